@@ -20,10 +20,18 @@ Multi-GPU: launched with torch.distributed.run, one process per GPU; clips are
 sharded (weak scaling, 32 per GPU); RCCL is used only for the final token-stream
 gather. value = audio seconds processed by all ranks / max-over-ranks time.
 
-Also reported: a roofline object for the dominant kernel (HIP events recorded
-by the engine on its own stream during the timed region) and a CPU baseline
-(the oracle — a CPU restatement of the reference path — timed on a bounded
-sample on this host).
+Also reported: a roofline object for the dominant kernel (timed by the engine
+on its own stream during the timed region).
+
+A plain run sets up, warms up, times the K steps and prints the line. --full
+adds the legs that take runs of their own: the one-lane pass after the timed
+region, the CPU baseline (the oracle — a CPU restatement of the reference
+path — timed on this host) and, for the default C3 configuration, the
+service-default leg in a child process.
+
+--dump-outputs DIR writes what the last timed step returned (every clip's
+token records as gathered on rank 0) to DIR/<name>.npy; the inputs are seeded,
+so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -234,7 +242,7 @@ def prosody_bench(args):
     """Segment prosody (k_prosody.hip through mwx_prosody_batch_device) over
     the segments of --clips clips per GPU (default 256 x 30 s), PCM and
     segment table resident in HBM; one launch per step, one workgroup per
-    segment. CPU baseline: the reference's own extract_prosody
+    segment. CPU baseline (--full): the reference's own extract_prosody
     (oracle/_ref) on a bounded sample of the same segments."""
     import ctypes
     import torch
@@ -305,8 +313,14 @@ def prosody_bench(args):
         work = 4 * int(desc[:, 1].sum())  # algorithmic: every sample read once
         achieved = work / avg_s / 1e9
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = prosody_cpu_baseline(pcm, desc)
+        if args.dump_outputs:
+            tags = d_out.cpu().numpy().view(np.int32).reshape(n_seg, -1)
+            # mwx_prosody: 16 f32 (8 features + the speaker vector), then gender / emotion /
+            # serial_runs / reserved as int32
+            write_dump(args.dump_outputs, {"prosody_features": tags[:, :16].copy().view(np.float32),
+                                           "prosody_tags": tags[:, 16:].astype(np.float32)})
         line = {
             "metric": "segment_prosody_audio_seconds_per_second",
             "value": round(audio_s / elapsed, 1),
@@ -410,6 +424,47 @@ def gather_summary(block, clips, per_clip):
     return {"clips": len(recs), "tokens": sum(len(r) for r in recs),
             "complete": len(recs) == clips and all(full(r) for r in recs),
             "records_crc32": f"{crc:08x}"}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def write_dump(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy (float32 / float64),
+    at most DUMP_MAX_BYTES in all. All arrays share their first axis (clips or
+    segments); a set over the limit is cut to a fixed, seeded sample of rows,
+    whose indices are written as sample_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes // max(1, n) for a in arrays.values()) + 8
+    if n * row_bytes > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // row_bytes,
+                                                       replace=False))
+        arrays = dict({k: a[keep] for k, a in arrays.items()},
+                      sample_rows=keep.astype(np.float64))
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+def dump_records(out_dir, block):
+    """The gathered record block of one step ([clips][1 + 4 * capacity] int32,
+    shard.pack_records) as the arrays a caller of the timed path receives:
+    token_count [clips]; token_id, token_t0, token_t1 (10-ms ticks) as float64
+    and token_p as float32, each [clips][longest clip], padded with -1 past a
+    clip's own count."""
+    import shard
+    block = np.asarray(block, np.int32)
+    cnt = block[:, 0]
+    width = max(1, int(cnt.max()) if len(cnt) else 1)
+    body = block[:, 1:1 + shard.RECORD_FIELDS * width].reshape(len(block), width, shard.RECORD_FIELDS)
+    live = np.arange(width)[None, :] < cnt[:, None]
+    arrays = {"token_count": cnt.astype(np.float64)}
+    for f, name in enumerate(("token_id", "token_t0", "token_t1")):
+        arrays[name] = np.where(live, body[:, :, f], -1).astype(np.float64)
+    p = np.ascontiguousarray(body[:, :, 3]).view(np.float32)
+    arrays["token_p"] = np.where(live, p, np.float32(-1)).astype(np.float32)
+    write_dump(out_dir, arrays)
 
 
 def launch_ranks(n):
@@ -627,6 +682,14 @@ def main():
     ap.add_argument("--steps", type=int, default=6,
                     help="timed batches (a multiple of --lanes keeps the lanes evenly loaded)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline, each a run of its own: the "
+                         "one-lane pass, the CPU baseline and (default C3 configuration) the "
+                         "service-default leg; --no-one-lane, --no-cpu-baseline and "
+                         "--no-service-leg take single ones out again")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's outputs (every clip's token "
+                         "records; --prosody: every segment's tags) as DIR/<name>.npy")
     ap.add_argument("--arch", default="large-v3")
     ap.add_argument("--wtype", default="bf16", choices=["bf16", "f16"])
     ap.add_argument("--clips", type=int, default=32, help="30-s clips per GPU")
@@ -646,9 +709,9 @@ def main():
                          "the temperature-fallback ladder (temperature_inc 0.2), token "
                          "timestamps, '-rich' weights decoded to the model's stop")
     ap.add_argument("--no-service-leg", action="store_true",
-                    help="skip the service-default leg the full default (C3) run reports beside its "
-                         "headline (one batch at --service-defaults, one lane, in a child process; "
-                         "--no-cpu-baseline quick runs skip it too)")
+                    help="with --full: skip the service-default leg the default (C3) run reports "
+                         "beside its headline (--service-defaults on two lanes, 2 timed batches "
+                         "after 1 warm-up, in a child process; --no-cpu-baseline skips it too)")
     ap.add_argument("--beam", type=int, default=0,
                     help="beam size (0: greedy; the service default is 5)")
     ap.add_argument("--clip-seconds", type=float, default=30.0,
@@ -659,7 +722,8 @@ def main():
                          "stream), as the SttEngine's parallel_requests batchers run them")
     ap.add_argument("--lane-stagger", type=float, default=0.0,
                     help="seconds lane i waits (x i) before its first timed batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-token-timestamps", action="store_true",
                     help="token_timestamps off (A/B only: the service sets it on)")
     ap.add_argument("--timing", choices=["span", "events"], default="span",
@@ -711,6 +775,13 @@ def main():
             dist.barrier()
 
     import mwx
+    import shard
+    from concurrent.futures import ThreadPoolExecutor
+    n_samp = int(args.clip_seconds * 16000)
+    # the seeded clips are synthesised on host threads (numpy releases the GIL) while the model
+    # file is written and loaded below: set-up time, outside the timed region
+    pool = ThreadPoolExecutor(max_workers=max(1, min(8, granted_cpus()[0])))
+    p16_jobs = [pool.submit(mwx.synth_pcm16, k, n_samp) for k in shard.clip_ids(rank, args.clips)]
     wt = mwx.GGML_BF16 if args.wtype == "bf16" else mwx.GGML_F16
     march = args.arch + ("-rich" if args.rich else "")
     path = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"mwx_bench_{march}_{args.wtype}.bin")
@@ -721,9 +792,9 @@ def main():
     barrier()
     ctx = mwx.Context.open(path, device=local,
                            compute=mwx.COMPUTE_MXFP8 if args.fp8 else mwx.COMPUTE_MODEL)
-    import shard
-    n_samp = int(args.clip_seconds * 16000)
-    pcms = [mwx.pcm16_to_f32(mwx.synth_pcm16(k, n_samp)) for k in shard.clip_ids(rank, args.clips)]
+    p16s = [j.result() for j in p16_jobs]
+    pool.shutdown()
+    pcms = [mwx.pcm16_to_f32(x) for x in p16s]
     p = ctx.default_params(mwx.SAMPLING_BEAM_SEARCH if args.beam > 1 else mwx.SAMPLING_GREEDY)
     if args.beam > 1:
         p.beam_search.beam_size = args.beam
@@ -750,7 +821,6 @@ def main():
     for i in range(lanes * args.clips):  # all states exist before any lane thread runs
         ctx.state(i)
     if args.host_input and args.pcm16:
-        p16s = [mwx.synth_pcm16(k, n_samp) for k in shard.clip_ids(rank, args.clips)]
         run_batch = lambda lane: ctx.full_batch_pcm16(p16s, p)  # noqa: E731
     elif args.host_input:
         run_batch = lambda lane: ctx.full_batch(pcms, p)  # noqa: E731
@@ -820,6 +890,7 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    last_timed = gathered.get("tokens")  # (the one-lane pass of --full gathers again)
     import ctypes
 
     def read_timed(states):
@@ -859,7 +930,7 @@ def main():
     if not args.decode_steps:
         n_windows = win_per_clip  # (encoder work: every decoded window is encoded)
     timed_1lane, steps_1lane, elapsed_1lane = None, 0, None
-    if lanes > 1 and not args.no_one_lane:
+    if args.full and lanes > 1 and not args.no_one_lane:
         # after the timed region (not part of `value`): the same batches on one
         # lane (B = 32 strictly one batch at a time), timed and with the
         # kernels' rooflines measured without another lane's kernels sharing
@@ -876,6 +947,8 @@ def main():
         timed_1lane = read_timed(owners[:1])
     if args.dump_gather and rank == 0 and gathered.get("tokens") is not None:
         np.save(args.dump_gather, gathered["tokens"])
+    if args.dump_outputs and rank == 0:
+        dump_records(args.dump_outputs, last_timed)
     if dist is not None:
         e = torch.tensor([elapsed], dtype=torch.float64, device=gdev or "cpu")
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
@@ -968,8 +1041,8 @@ def main():
                           "ms_per_step": round(elapsed_1lane / steps_1lane * 1e3, 2),
                           "roofline": r1, "roofline_encoder": e1}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            # all cores granted to this job (the GPU box: 16 per GPU, OMP_NUM_THREADS)
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            # all cores granted to this job (the affinity mask, capped by OMP_NUM_THREADS)
             threads = granted_cpus()[0]
             try:
                 sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -1022,7 +1095,7 @@ def main():
         }
     ctx.close()
     if rank == 0:
-        if world == 1 and is_headline_config(args):
+        if args.full and world == 1 and is_headline_config(args):
             line["service_defaults"] = service_leg()
         print(json.dumps(line), flush=True)
     if dist is not None:

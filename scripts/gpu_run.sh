@@ -112,8 +112,8 @@ for s in "$@"; do
     barprobe) run barprobe 120 ./scripts/probe/xcd_barrier_probe 4000 ;;
     tests) run tests 1150 python -u -m pytest tests -m gpu -v -s -rf --durations=0 --timeout 600 --timeout-method thread ;;
     smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python -u bench.py --steps 20 --warmup 5 ;;
-    benchq) run benchq 400 python -u bench.py --steps 8 --warmup 2 --no-cpu-baseline ;;
+    bench) run bench 600 python -u bench.py --full --steps 20 --warmup 5 ;;
+    benchq) run benchq 400 python -u bench.py --full --steps 8 --warmup 2 --no-cpu-baseline ;;
     bench1) run bench1 400 python -u bench.py --lanes 1 --steps 4 --warmup 1 --no-cpu-baseline ;;
     c2) run c2 300 python -u bench.py --arch base --wtype f16 --clips 1 --lanes 1 --steps 20 --warmup 3 --no-cpu-baseline ;;
     c2nt) run c2nt 300 env MWX_XATTN_NT=1 python -u bench.py --arch base --wtype f16 --clips 1 --lanes 1 --steps 20 --warmup 3 --no-cpu-baseline ;;
@@ -160,13 +160,13 @@ for s in "$@"; do
     bench1g32) run bench1g32 400 env MWX_GEMM_GROUP=32 python -u bench.py --lanes 1 --steps 4 --warmup 1 --no-cpu-baseline ;;
     pmcg32) (export MWX_GEMM_GROUP=32; cd /tmp && run pmcg32_FETCH_SIZE 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/${TAG}_pmcg32_FETCH_SIZE" -o pmc -- $B --lanes 1 --steps 1 --warmup 0 --decode-steps 8 --no-cpu-baseline) || exit 5 ;;
     bench1nts) run bench1nts 400 python -u bench.py --lanes 1 --steps 4 --warmup 1 --no-cpu-baseline --no-token-timestamps ;;
-    benchqnts) run benchqnts 400 python -u bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-token-timestamps ;;
+    benchqnts) run benchqnts 400 python -u bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-token-timestamps ;;
     probe) run probe 200 env PROBE_ONLY=seam ./scripts/probe/dec_chain_probe 32 10 && run probel 200 env PROBE_ONLY=layer ./scripts/probe/dec_chain_probe 32 10 ;;
-    benchqnp) run benchqnp 400 env MWX_PERF_PERIOD=1000000 python -u bench.py --steps 8 --warmup 2 --no-cpu-baseline ;;
+    benchqnp) run benchqnp 400 env MWX_PERF_PERIOD=1000000 python -u bench.py --full --steps 8 --warmup 2 --no-cpu-baseline ;;
     bench1np8) run bench1np8 400 env MWX_PERF_PERIOD=1000000 python -u bench.py --lanes 1 --steps 4 --warmup 1 --no-cpu-baseline ;;
-    b5) run b5 500 python -u bench.py --beam 5 --steps 4 --warmup 1 --no-cpu-baseline ;;
-    c5) run c5 700 python -u bench.py --fp8 --beam 5 --clip-seconds 600 --steps 2 --warmup 1 --no-cpu-baseline ;;
-    prompt) run prompt 700 python -u bench.py --prompt-leg --steps 2 --warmup 1 --no-cpu-baseline ;;
+    b5) run b5 500 python -u bench.py --full --beam 5 --steps 4 --warmup 1 --no-cpu-baseline ;;
+    c5) run c5 700 python -u bench.py --full --fp8 --beam 5 --clip-seconds 600 --steps 2 --warmup 1 --no-cpu-baseline ;;
+    prompt) run prompt 700 python -u bench.py --full --prompt-leg --steps 2 --warmup 1 --no-cpu-baseline ;;
     prof) (cd /tmp && run prof 600 rocprofv3 --kernel-trace --stats -d "$O/${TAG}_prof" -o prof -- $B --steps 4 --warmup 2 --no-cpu-baseline --no-one-lane) || exit 4; python3 scripts/prof_box.py "$O/${TAG}_prof" || exit 4 ;;
     prof1) (cd /tmp && run prof1 600 rocprofv3 --kernel-trace --stats -d "$O/${TAG}_prof1" -o prof -- $B --lanes 1 --steps 2 --warmup 1 --no-cpu-baseline) || exit 4; python3 scripts/prof_box.py "$O/${TAG}_prof1" || exit 4 ;;
     profc2) (cd /tmp && run profc2 400 rocprofv3 --kernel-trace --stats -d "$O/${TAG}_profc2" -o prof -- $B --arch base --wtype f16 --clips 1 --lanes 1 --steps 5 --warmup 2 --no-cpu-baseline) || exit 4; python3 scripts/prof_box.py "$O/${TAG}_profc2" || exit 4 ;;

@@ -19,9 +19,12 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "sentiric-stt-whisper-service_amd"))
 import orc  # noqa: E402
 
 OUT = os.path.join(HERE, "prosody_ref.npz")
+MORE = os.path.join(HERE, "prosody_ref_more.npz")
+MORE_OPTS = ((0.07, 170.0, 60.0, 500.0), (0.13, 190.0, 70.0, 450.0))
 
 
 def voice(rng, n, sr, f0, amp, hnum=6, jitter=0.0, noise=0.0, rate=4.0):
@@ -120,8 +123,58 @@ def ref_cluster_ids(L, vecs, thr):
     return ids
 
 
+def extra_cases():
+    """Seeded inputs beyond the fixture: synthetic speech clips cut at random
+    ranges (up to 30 s), pure tones on the f0 grid, noise, silence runs.
+    Too long to store: generated (seeded) where they are used; only the
+    reference's results for them are stored (prosody_ref_more.npz)."""
+    import mwx
+    rng = np.random.default_rng(1234)
+    out = []
+    clip = mwx.pcm16_to_f32(mwx.synth_pcm16(11, n=30 * 16000))
+    out.append(clip)
+    for _ in range(12):
+        n = int(rng.integers(160, 160000))
+        s = int(rng.integers(0, len(clip) - n))
+        out.append(clip[s:s + n])
+    t = np.arange(16000) / 16000.0
+    for f in (99.5, 100.0, 150.0, 300.0, 480.0, 520.0):
+        out.append((0.3 * np.sin(2 * np.pi * f * t)).astype(np.float32))
+    out.append(rng.normal(0, 0.05, 24000).astype(np.float32))
+    sil = np.zeros(20000, np.float32)
+    out.append(np.concatenate([clip[:30000], sil, clip[30000:60000]]))
+    return out
+
+
+def extra_cluster_trials():
+    """20 seeded (vectors, threshold) clustering runs: 60 noisy draws from 1-5
+    centres, one zero vector among them."""
+    rng = np.random.default_rng(99)
+    out = []
+    for trial in range(20):
+        centers = rng.uniform(0, 1, (int(rng.integers(1, 6)), 8)).astype(np.float32)
+        vecs = np.array([centers[rng.integers(len(centers))] + rng.normal(0, 0.05, 8)
+                         for _ in range(60)], np.float32)
+        vecs[rng.integers(60)] = 0
+        out.append((vecs, float(rng.choice([0.5, 0.88, 0.95, 0.99]))))
+    return out
+
+
+def main_more(L):
+    """prosody_ref_more.npz: the reference's results for extra_cases() at
+    MORE_OPTS and for extra_cluster_trials()."""
+    res = [[ref_prosody(L, x, 16000, o) for o in MORE_OPTS] for x in extra_cases()]
+    ids = np.array([ref_cluster_ids(L, v, thr) for v, thr in extra_cluster_trials()])
+    np.savez_compressed(MORE, bits=np.array([[r[0] for r in row] for row in res], np.uint32),
+                        gender=np.array([[r[1] for r in row] for row in res], np.int32),
+                        emotion=np.array([[r[2] for r in row] for row in res], np.int32),
+                        cluster_ids=ids)
+    print(f"{MORE}: {len(res)} x {len(MORE_OPTS)} prosody results, {ids.shape} cluster ids")
+
+
 def main():
     L = load_ref()
+    main_more(L)
     cs = cases()
     pcm = np.concatenate([c[0] for c in cs])
     lens = np.array([len(c[0]) for c in cs], np.int64)

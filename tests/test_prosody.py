@@ -5,8 +5,9 @@ src/stt_engine.cpp:313-337).
 Bar: bit-exact. The golden vectors (tests/golden/prosody_ref.npz) were made by
 the reference's own code compiled unchanged (oracle/_ref, see
 tests/golden/make_prosody_golden.py); the oracle restatement
-(oracle/prosody_oracle.cpp) is pinned to them and, where oracle/_ref is built,
-to the reference on further seeded inputs. The GPU kernel (k_prosody.hip,
+(oracle/prosody_oracle.cpp) is pinned to them, to the reference's stored
+results for further seeded inputs (tests/golden/prosody_ref_more.npz) and,
+where oracle/_ref is built, to the reference itself on those. The GPU kernel (k_prosody.hip,
 through the C ABI mwx_prosody_batch) and the host SttEngine's clusterer are
 checked against both."""
 import ctypes as C
@@ -20,6 +21,7 @@ import orc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "prosody_ref.npz")
+MORE = os.path.join(ROOT, "tests", "golden", "prosody_ref_more.npz")
 REF = os.path.join(ROOT, "oracle", "_ref", "libref_prosody.so")
 STT = os.path.join(ROOT, "sentiric-stt-whisper-service_amd", "libmwx_stt.so")
 
@@ -55,35 +57,26 @@ def golden_cases(G):
         yield i, G["pcm16"][s:s + n], int(G["sample_rate"][i]), tuple(float(x) for x in G["opts"][i])
 
 
-def ref_lib():
-    if not os.path.exists(REF):
-        return None
+def golden_module():
     import importlib.util
     spec = importlib.util.spec_from_file_location(
         "make_prosody_golden", os.path.join(ROOT, "tests", "golden", "make_prosody_golden.py"))
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)
+    return m
+
+
+def ref_lib():
+    if not os.path.exists(REF):
+        return None
+    m = golden_module()
     return m, m.load_ref()
 
 
 def extra_cases():
-    """Seeded inputs beyond the fixture: synthetic speech clips cut at random
-    ranges (up to 30 s), pure tones on the f0 grid, noise, silence runs."""
-    rng = np.random.default_rng(1234)
-    out = []
-    clip = mwx.pcm16_to_f32(mwx.synth_pcm16(11, n=30 * 16000))
-    out.append(clip)
-    for _ in range(12):
-        n = int(rng.integers(160, 160000))
-        s = int(rng.integers(0, len(clip) - n))
-        out.append(clip[s:s + n])
-    t = np.arange(16000) / 16000.0
-    for f in (99.5, 100.0, 150.0, 300.0, 480.0, 520.0):
-        out.append((0.3 * np.sin(2 * np.pi * f * t)).astype(np.float32))
-    out.append(rng.normal(0, 0.05, 24000).astype(np.float32))
-    sil = np.zeros(20000, np.float32)
-    out.append(np.concatenate([clip[:30000], sil, clip[30000:60000]]))
-    return out
+    """Seeded inputs beyond the fixture (make_prosody_golden.extra_cases); the
+    reference's results for them are stored in prosody_ref_more.npz."""
+    return golden_module().extra_cases()
 
 
 # ---------------------------------------------------------------- CPU -----
@@ -99,14 +92,18 @@ def test_oracle_matches_reference_golden_vectors():
 
 
 def test_oracle_matches_reference_build_on_more_inputs():
-    r = ref_lib()
-    if r is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    m, L = r
-    for k, x in enumerate(extra_cases()):
-        for opts in ((0.07, 170.0, 60.0, 500.0), (0.13, 190.0, 70.0, 450.0)):
-            wb, wg, we = m.ref_prosody(L, x, 16000, opts)
-            assert_same(orc.prosody(x, 16000, *opts), wb, wg, we, f"extra {k} {opts}")
+    """Against the reference's stored results for the further inputs and,
+    where oracle/_ref is built, against the reference itself."""
+    m, M, r = golden_module(), np.load(MORE), ref_lib()
+    xs = m.extra_cases()
+    assert M["bits"].shape == (len(xs), len(m.MORE_OPTS), 16)
+    for k, x in enumerate(xs):
+        for j, opts in enumerate(m.MORE_OPTS):
+            got = orc.prosody(x, 16000, *opts)
+            assert_same(got, M["bits"][k, j], int(M["gender"][k, j]), int(M["emotion"][k, j]),
+                        f"extra {k} {opts}")
+            if r is not None:
+                assert_same(got, *m.ref_prosody(r[1], x, 16000, opts), f"extra {k} {opts} vs ref")
 
 
 def _host_cluster_ids(vecs, thr):
@@ -131,19 +128,16 @@ def test_speaker_clustering_matches_reference_golden():
 
 
 def test_speaker_clustering_matches_reference_build():
-    r = ref_lib()
-    if r is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    m, L = r
-    rng = np.random.default_rng(99)
-    for trial in range(20):
-        centers = rng.uniform(0, 1, (int(rng.integers(1, 6)), 8)).astype(np.float32)
-        vecs = np.array([centers[rng.integers(len(centers))] + rng.normal(0, 0.05, 8)
-                         for _ in range(60)], np.float32)
-        vecs[rng.integers(60)] = 0
-        thr = float(rng.choice([0.5, 0.88, 0.95, 0.99]))
-        want = m.ref_cluster_ids(L, vecs, thr)
-        assert _host_cluster_ids(vecs, thr) == want, trial
+    """Seeded clustering runs against the reference's stored ids and, where
+    oracle/_ref is built, against the reference itself."""
+    m, M, r = golden_module(), np.load(MORE), ref_lib()
+    trials = m.extra_cluster_trials()
+    assert len(M["cluster_ids"]) == len(trials) == 20
+    for trial, (vecs, thr) in enumerate(trials):
+        got = _host_cluster_ids(vecs, thr)
+        assert got == M["cluster_ids"][trial].tolist(), trial
+        if r is not None:
+            assert got == m.ref_cluster_ids(r[1], vecs, thr), trial
 
 
 def test_prosody_abi_declared():
