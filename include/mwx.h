@@ -29,6 +29,8 @@
  * batched GPU pass (the data-parallel unit of this engine), and
  * mwx_write_synthetic_model writes a seeded model in the ggml .bin layout that
  * src/model_manager.cpp provisions (no real checkpoints exist offline).
+ * The whisper_vad_* family (src/stt_engine.cpp:44-55, :108-115) maps to
+ * mwx_vad_*: see the voice-activity section below.
  *
  * Conventions: plain C, no exceptions cross this boundary, all functions return
  * NULL / negative on failure (0 = success), strings returned by getters stay
@@ -294,6 +296,64 @@ long mwx_resample_max_frames(int n_in, int src_rate, int dst_rate); /* (long)(n_
 int mwx_resample(struct mwx_context* ctx, struct mwx_state* state, const float* in, int n_in,
                  int src_rate, int dst_rate, float* out, int out_cap);
 
+/* --- voice-activity detection ---------------------------------------------
+ * The whisper_vad_* calls behind SttEngine::is_speech_detected
+ * (src/stt_engine.cpp:44-55 load, :108-115 call), on the GPU:
+ *
+ *   mwx_vad_default_context_params     <- whisper_vad_default_context_params
+ *   mwx_vad_init_from_file_with_params <- whisper_vad_init_from_file_with_params
+ *   mwx_vad_detect_speech              <- whisper_vad_detect_speech
+ *   mwx_vad_n_probs / mwx_vad_probs    <- whisper_vad_n_probs / whisper_vad_probs
+ *   mwx_vad_free                       <- whisper_vad_free
+ *
+ * The model is a Silero-v5-shaped net over 512-sample chunks of 16 kHz f32
+ * PCM (the last chunk zero-padded): one speech probability per chunk, the
+ * LSTM state zero at the start of every clip of every call. The network and
+ * the file layout are written down in INTEGRATION.md ("VAD model"); upstream
+ * whisper.cpp is not available to this project, so parity with its VAD is
+ * unpinned.
+ *
+ * One call at a time per context (the host SttEngine holds a mutex, as the
+ * reference does, src/stt_engine.cpp:110). `samples` may be host memory or
+ * device memory of the context's GPU, as for mwx_full_batch. */
+struct mwx_vad_context;
+struct mwx_vad_context_params {
+  int n_threads;  /* accepted for API parity; unused */
+  bool use_gpu;   /* must be true: there is no CPU path */
+  int gpu_device; /* HIP device ordinal */
+};
+struct mwx_vad_context_params mwx_vad_default_context_params(void);
+/* NULL (with a logged reason) on a bad magic, a truncated file, a missing or
+ * mis-shaped tensor, hyper-parameters other than the supported shape, or a
+ * device error. */
+struct mwx_vad_context* mwx_vad_init_from_file_with_params(
+    const char* path_model, struct mwx_vad_context_params params);
+void mwx_vad_free(struct mwx_vad_context* vctx);
+
+/* Computes the chunk probabilities of one clip. Returns true when they were
+ * computed and false on an error. The return value is NOT a speech decision:
+ * read the probabilities and apply a rule (SttEngine: any chunk >=
+ * vad_threshold). n_samples = 0 succeeds with 0 probabilities. */
+bool mwx_vad_detect_speech(struct mwx_vad_context* vctx, const float* samples, int n_samples);
+int mwx_vad_n_probs(struct mwx_vad_context* vctx);
+/* Valid until the next call on the same context. */
+const float* mwx_vad_probs(struct mwx_vad_context* vctx);
+
+/* Engine extension: all clips in one pass (the front end over every chunk of
+ * every clip at once, the recurrences of the clips side by side). Clip b's
+ * mwx_vad_n_chunks(n_samples[b]) probabilities are written to
+ * probs_out + probs_offset[b] (host memory, sized by the caller); bit for bit
+ * what mwx_vad_detect_speech gives for the clip alone. Leaves
+ * mwx_vad_n_probs / mwx_vad_probs unchanged. Returns 0, or < 0 on bad
+ * arguments or a device error. */
+int mwx_vad_n_chunks(int n_samples); /* ceil(n_samples / 512) */
+int mwx_vad_detect_speech_batch(struct mwx_vad_context* vctx, const float* const* samples,
+                                const int* n_samples, int n_clips, float* probs_out,
+                                const int* probs_offset);
+/* Device time of the last call's two kernels (front end; recurrence + head)
+ * in milliseconds, from HIP events on the context's stream. 0 on success. */
+int mwx_vad_last_kernel_ms(struct mwx_vad_context* vctx, float* frontend_ms, float* lstm_ms);
+
 /* --- vocabulary / model ------------------------------------------------- */
 const char* mwx_token_to_str(struct mwx_context* ctx, mwx_token token);
 mwx_token mwx_token_eot(struct mwx_context* ctx);
@@ -345,6 +405,14 @@ int mwx_perf_read_class(struct mwx_state* state, const char* kernel_class, doubl
  * Returns 0 on success. */
 int mwx_write_synthetic_model(const char* path, const char* arch, int wtype,
                               uint64_t seed);
+
+/* Writes a seeded VAD model in the layout mwx_vad_init_from_file_with_params
+ * reads ("VAD model"): the STFT basis is the Hann-windowed
+ * DFT, every other weight is uniform in +-g / sqrt(fan_in) (g = 2 encoder,
+ * 3 LSTM, 16 head: at g = 1 a random net barely reacts to its input). The
+ * basis and the convolution weights are f16, the rest f32. Returns 0 on
+ * success. */
+int mwx_write_synthetic_vad_model(const char* path, uint64_t seed);
 
 /* Quantizes a whisper ggml .bin (f32 / f16 / bf16) into a ggml block type
  * (q4_0 = 2, q4_1 = 3, q5_0 = 6, q5_1 = 7, q8_0 = 8; the 256-element K types

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <map>
+#include <mutex>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -122,6 +123,15 @@ std::vector<int32_t> tokenize(const Vocab& vocab, const std::string& text);
 
 // Logging (whisper_log_set compatible).
 void log_msg(mwx_log_level level, const char* fmt, ...);
+
+// Seeding of the synthetic model writers (model.cpp, vad.cpp): element i of
+// tensor `name` draws splitmix64((fnv1a64(name) ^ seed) + i * 0xD1B54A32D192ED03).
+uint64_t splitmix64(uint64_t x);
+uint64_t fnv1a64(const std::string& s);
+
+// Process-wide order between graph capture and device (de)allocation
+// (engine.cpp).
+std::recursive_mutex& capture_mutex();
 
 // f32 <-> 16-bit float helpers (round to nearest even).
 uint16_t f32_to_f16(float f);

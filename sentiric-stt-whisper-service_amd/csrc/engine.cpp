@@ -67,7 +67,7 @@ inline bool ln_fold_on() {
 // SttEngine's parallel_requests batchers) capture their decode graphs while
 // another batch may be growing its buffers, so both hold this lock
 // (recursive: a capture may grow a buffer of its own).
-inline std::recursive_mutex& capture_mutex() {
+std::recursive_mutex& capture_mutex() {
   static std::recursive_mutex m;
   return m;
 }

@@ -1,0 +1,263 @@
+// Voice-activity detection on gfx950: a Silero-v5-shaped network (INTEGRATION.md,
+// "VAD model") over 512-sample chunks of 16 kHz PCM, one speech probability per
+// chunk. Replaces the whisper_vad_* calls behind SttEngine::is_speech_detected
+// (src/stt_engine.cpp:108-115), which the reference runs on the CPU one clip
+// at a time.
+//
+// Two kernels:
+//   vad_frontend_kernel — everything that does not depend on the LSTM state,
+//     for every chunk of every clip of the call at once: reflect padding, the
+//     STFT magnitude, four kernel-3 convolutions with ReLU and the LSTM input
+//     projection W_ih x + b_ih + b_hh. A workgroup takes VAD_TILE consecutive
+//     chunks of one clip so that each weight it loads is used for all of them;
+//     the activations of the tile live in LDS.
+//   vad_lstm_kernel — the 128-wide recurrence and the head, one workgroup per
+//     clip: 512 threads, thread j keeps row j of W_hh in registers for the
+//     whole clip, h is broadcast through LDS.
+//
+// All arithmetic is f32. Every output is one fixed chain of fmaf over its
+// inputs in index order, so a chunk's result does not depend on its slot in a
+// tile or on which other clips are in the launch: a batch gives the bits of
+// the single calls.
+#include "kcommon.h"
+#include "kernels.h"
+
+namespace mwx {
+
+namespace {
+
+constexpr int VAD_FE_THREADS = 256;
+constexpr int VAD_XP = VAD_CHUNK + 2 * VAD_PAD;  // 640 padded samples
+constexpr int VAD_ROWS = 2 * VAD_BINS;           // 258 basis rows
+constexpr int VAD_FRAMES = 4;
+// per-chunk LDS: A holds the raw STFT [258][4] (then conv1 / conv3 outputs),
+// B the padded samples [640] (then magnitude [129][4], conv2 / conv4 outputs)
+constexpr int VAD_LA = VAD_ROWS * VAD_FRAMES;  // 1032 floats
+constexpr int VAD_LB = VAD_XP;                 // 640 floats
+
+__device__ __forceinline__ float sigmoidf_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// Kernel-3, zero-pad-1 convolution + bias + ReLU over the tile: in
+// [chunk][CIN][FIN] (chunk stride in_cs) -> out [chunk][COUT][FOUT] (chunk
+// stride out_cs), weights wt [(ci * 3 + k)][COUT]. Thread = one output channel
+// of VAD_TILE / (256 / COUT) chunks; taps that fall into the padding are
+// skipped at compile time.
+template <int CIN, int COUT, int FIN, int FOUT, int STRIDE>
+__device__ __forceinline__ void vad_conv(const float* __restrict__ wt, const float* __restrict__ bias,
+                                         const float* in, int in_cs, float* out, int out_cs) {
+  constexpr int G = VAD_FE_THREADS / COUT;  // chunk groups
+  constexpr int CPG = VAD_TILE / G;         // chunks per thread
+  static_assert(G * COUT == VAD_FE_THREADS && CPG * G == VAD_TILE, "tile split");
+  const int o = threadIdx.x % COUT, c0 = (threadIdx.x / COUT) * CPG;
+  float acc[CPG][FOUT];
+#pragma unroll
+  for (int c = 0; c < CPG; ++c)
+#pragma unroll
+    for (int f = 0; f < FOUT; ++f) acc[c][f] = 0.0f;
+  for (int ci = 0; ci < CIN; ++ci) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float w = wt[(ci * 3 + k) * COUT + o];
+#pragma unroll
+      for (int c = 0; c < CPG; ++c)
+#pragma unroll
+        for (int f = 0; f < FOUT; ++f) {
+          const int pos = f * STRIDE + k - 1;
+          if (pos >= 0 && pos < FIN)
+            acc[c][f] = fmaf(w, in[(c0 + c) * in_cs + ci * FIN + pos], acc[c][f]);
+        }
+    }
+  }
+  const float b = bias[o];
+#pragma unroll
+  for (int c = 0; c < CPG; ++c)
+#pragma unroll
+    for (int f = 0; f < FOUT; ++f)
+      out[(c0 + c) * out_cs + o * FOUT + f] = fmaxf(acc[c][f] + b, 0.0f);
+}
+
+}  // namespace
+
+// grid.x = n_clips * tiles (tiles = ceil(max_chunks / VAD_TILE)); workgroup
+// (clip b, tile x) handles chunks [x * VAD_TILE, ...) of clip b and leaves at
+// once when the clip has fewer. Chunks of the tile past the clip's last are
+// computed on zeros and not stored.
+__global__ __launch_bounds__(VAD_FE_THREADS) void vad_frontend_kernel(
+    VadWeights W, const float* const* __restrict__ pcm, const int* __restrict__ n_samples,
+    const int* __restrict__ chunk_off, int n_clips, int tiles, float* __restrict__ pre) {
+  __shared__ __attribute__((aligned(16))) float sA[VAD_TILE * VAD_LA];
+  __shared__ __attribute__((aligned(16))) float sB[VAD_TILE * VAD_LB];
+  const int b = blockIdx.x / tiles;
+  const int n0 = (blockIdx.x % tiles) * VAD_TILE;
+  if (b >= n_clips) return;
+  const int off = chunk_off[b];
+  const int nch = chunk_off[b + 1] - off;  // chunks of this clip
+  if (n0 >= nch) return;
+  const int t = threadIdx.x;
+
+  // padded samples: chunk-local index s in [-64, 576) reflects about 0 and 511
+  // (edge not repeated); samples past the clip's end are zero
+  {
+    const float* __restrict__ x = pcm[b];
+    const long ns = n_samples[b];
+    for (int idx = t; idx < VAD_TILE * VAD_XP; idx += VAD_FE_THREADS) {
+      const int c = idx / VAD_XP, p = idx % VAD_XP;
+      int s = p - VAD_PAD;
+      if (s < 0) s = -s;
+      if (s >= VAD_CHUNK) s = 2 * (VAD_CHUNK - 1) - s;
+      const long gi = (long)(n0 + c) * VAD_CHUNK + s;
+      sB[c * VAD_LB + p] = (n0 + c < nch && gi < ns) ? x[gi] : 0.0f;
+    }
+  }
+  __syncthreads();
+
+  // STFT: raw[c][row][f] = sum_tap basis[row][tap] * x[c][128 f + tap].
+  // Thread t takes row t for the whole tile; rows 256, 257 are split by
+  // (row, chunk, frame) over 64 threads afterwards (the same chain per output).
+  {
+    float acc[VAD_TILE][VAD_FRAMES];
+#pragma unroll
+    for (int c = 0; c < VAD_TILE; ++c)
+#pragma unroll
+      for (int f = 0; f < VAD_FRAMES; ++f) acc[c][f] = 0.0f;
+    for (int tap = 0; tap < VAD_NFFT; tap += 4) {
+      float w[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) w[u] = W.basis_t[(tap + u) * VAD_ROWS + t];
+#pragma unroll
+      for (int c = 0; c < VAD_TILE; ++c)
+#pragma unroll
+        for (int f = 0; f < VAD_FRAMES; ++f) {
+          const float4 xv = *reinterpret_cast<const float4*>(&sB[c * VAD_LB + 128 * f + tap]);
+          float a = acc[c][f];
+          a = fmaf(w[0], xv.x, a);
+          a = fmaf(w[1], xv.y, a);
+          a = fmaf(w[2], xv.z, a);
+          a = fmaf(w[3], xv.w, a);
+          acc[c][f] = a;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < VAD_TILE; ++c)
+      *reinterpret_cast<float4*>(&sA[c * VAD_LA + t * VAD_FRAMES]) =
+          make_float4(acc[c][0], acc[c][1], acc[c][2], acc[c][3]);
+    if (t < (VAD_ROWS - VAD_FE_THREADS) * VAD_TILE * VAD_FRAMES) {
+      const int row = VAD_FE_THREADS + t / (VAD_TILE * VAD_FRAMES);
+      const int c = (t / VAD_FRAMES) % VAD_TILE, f = t % VAD_FRAMES;
+      float a = 0.0f;
+      for (int tap = 0; tap < VAD_NFFT; ++tap)
+        a = fmaf(W.basis_t[tap * VAD_ROWS + row], sB[c * VAD_LB + 128 * f + tap], a);
+      sA[c * VAD_LA + row * VAD_FRAMES + f] = a;
+    }
+  }
+  __syncthreads();
+
+  // magnitude [c][bin][f] -> B
+  for (int idx = t; idx < VAD_TILE * VAD_BINS * VAD_FRAMES; idx += VAD_FE_THREADS) {
+    const int c = idx / (VAD_BINS * VAD_FRAMES), r = idx % (VAD_BINS * VAD_FRAMES);
+    const float re = sA[c * VAD_LA + r], im = sA[c * VAD_LA + VAD_BINS * VAD_FRAMES + r];
+    sB[c * VAD_LB + r] = sqrtf(re * re + im * im);
+  }
+  __syncthreads();
+
+  // encoder: 129 -> 128 (s1), 128 -> 64 (s2), 64 -> 64 (s2), 64 -> 128 (s1);
+  // frames 4 -> 4 -> 2 -> 1 -> 1
+  vad_conv<129, 128, 4, 4, 1>(W.conv_t[0], W.conv_b[0], sB, VAD_LB, sA, VAD_LA);
+  __syncthreads();
+  vad_conv<128, 64, 4, 2, 2>(W.conv_t[1], W.conv_b[1], sA, VAD_LA, sB, VAD_LB);
+  __syncthreads();
+  vad_conv<64, 64, 2, 1, 2>(W.conv_t[2], W.conv_b[2], sB, VAD_LB, sA, VAD_LA);
+  __syncthreads();
+  vad_conv<64, 128, 1, 1, 1>(W.conv_t[3], W.conv_b[3], sA, VAD_LA, sB, VAD_LB);
+  __syncthreads();
+
+  // LSTM input projection: pre[chunk][j] = W_ih[j] . x + b_ih[j] + b_hh[j]
+  for (int j = t; j < VAD_GATES; j += VAD_FE_THREADS) {
+    float acc[VAD_TILE];
+#pragma unroll
+    for (int c = 0; c < VAD_TILE; ++c) acc[c] = 0.0f;
+    for (int i = 0; i < VAD_HID; ++i) {
+      const float w = W.wih_t[i * VAD_GATES + j];
+#pragma unroll
+      for (int c = 0; c < VAD_TILE; ++c) acc[c] = fmaf(w, sB[c * VAD_LB + i], acc[c]);
+    }
+    const float bi = W.b_ih[j], bh = W.b_hh[j];
+#pragma unroll
+    for (int c = 0; c < VAD_TILE; ++c)
+      if (n0 + c < nch) pre[(size_t)(off + n0 + c) * VAD_GATES + j] = (acc[c] + bi) + bh;
+  }
+}
+
+// One workgroup per clip. Step: every thread adds its W_hh row . h to its
+// pre-activation and posts the gate in LDS; after the barrier threads 0..127
+// (waves 0, 1) update c and h for their unit, publish h and reduce
+// w_f . relu(h); after the second barrier thread 0 writes the probability.
+__global__ __launch_bounds__(VAD_GATES) void vad_lstm_kernel(
+    const float* __restrict__ whh_t, const float* __restrict__ w_f, float b_f,
+    const float* __restrict__ pre, const int* __restrict__ chunk_off, int n_clips,
+    float* __restrict__ probs) {
+  __shared__ __attribute__((aligned(16))) float sh[VAD_HID];
+  __shared__ float sg[VAD_GATES];
+  __shared__ float sp[2];
+  const int b = blockIdx.x;
+  if (b >= n_clips) return;
+  const int off = chunk_off[b];
+  const int nch = chunk_off[b + 1] - off;
+  if (nch <= 0) return;
+  const int j = threadIdx.x;
+  float w[VAD_HID];
+#pragma unroll
+  for (int k = 0; k < VAD_HID; ++k) w[k] = whh_t[k * VAD_GATES + j];
+  const float wf = j < VAD_HID ? w_f[j] : 0.0f;
+  float c = 0.0f;
+  if (j < VAD_HID) sh[j] = 0.0f;
+  __syncthreads();
+  const float* __restrict__ pj = pre + (size_t)off * VAD_GATES + j;
+  float nxt = pj[0];
+  for (int s = 0; s < nch; ++s) {
+    const float cur = nxt;
+    if (s + 1 < nch) nxt = pj[(size_t)(s + 1) * VAD_GATES];
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+#pragma unroll
+    for (int q = 0; q < VAD_HID / 4; ++q) {
+      const float4 hv = *reinterpret_cast<const float4*>(&sh[4 * q]);
+      a0 = fmaf(w[4 * q + 0], hv.x, a0);
+      a1 = fmaf(w[4 * q + 1], hv.y, a1);
+      a2 = fmaf(w[4 * q + 2], hv.z, a2);
+      a3 = fmaf(w[4 * q + 3], hv.w, a3);
+    }
+    sg[j] = cur + ((a0 + a1) + (a2 + a3));
+    __syncthreads();  // gates posted; every read of h for this step is done
+    if (j < VAD_HID) {
+      const float gi = sigmoidf_acc(sg[j]);
+      const float gf = sigmoidf_acc(sg[VAD_HID + j]);
+      const float gg = tanhf(sg[2 * VAD_HID + j]);
+      const float go = sigmoidf_acc(sg[3 * VAD_HID + j]);
+      c = gf * c + gi * gg;
+      const float h = go * tanhf(c);
+      sh[j] = h;
+      const float part = wave_sum(wf * fmaxf(h, 0.0f));
+      if ((j & 63) == 0) sp[j >> 6] = part;
+    }
+    __syncthreads();  // h and the head's two partial sums posted
+    if (j == 0) probs[(size_t)off + s] = sigmoidf_acc((sp[0] + sp[1]) + b_f);
+  }
+}
+
+void vad_frontend_launch(const VadWeights& w, const float* const* pcm, const int* n_samples,
+                         const int* chunk_off, int n_clips, int max_chunks, float* pre,
+                         hipStream_t st) {
+  if (n_clips <= 0 || max_chunks <= 0) return;
+  const int tiles = (max_chunks + VAD_TILE - 1) / VAD_TILE;
+  vad_frontend_kernel<<<(unsigned)((long)n_clips * tiles), VAD_FE_THREADS, 0, st>>>(
+      w, pcm, n_samples, chunk_off, n_clips, tiles, pre);
+}
+
+void vad_lstm_launch(const VadWeights& w, const float* pre, const int* chunk_off, int n_clips,
+                     float* probs, hipStream_t st) {
+  if (n_clips <= 0) return;
+  vad_lstm_kernel<<<n_clips, VAD_GATES, 0, st>>>(w.whh_t, w.w_f, w.b_f, pre, chunk_off, n_clips,
+                                                 probs);
+}
+
+}  // namespace mwx

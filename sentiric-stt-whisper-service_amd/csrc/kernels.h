@@ -460,4 +460,36 @@ void prosody_launch(const float* pcm, const ProsodySeg* seg, int n_seg, float* f
                     float4* feat, int* fcyc, ProsodyOut* out, int frame, int sample_rate, float alpha,
                     float gender_thr, float min_pitch, float max_pitch, hipStream_t st);
 
+// Voice-activity detection (k_vad.hip): a Silero-v5-shaped net over 512-sample
+// chunks. Weights are f32, transposed at load so that the output row is the
+// contiguous index (lane = output row reads coalesced).
+constexpr int VAD_CHUNK = 512;   // samples per chunk / probability
+constexpr int VAD_PAD = 64;      // reflect padding on each side
+constexpr int VAD_NFFT = 256;    // STFT taps (stride 128: 4 frames per chunk)
+constexpr int VAD_BINS = 129;    // rows 0..128 real, 129..257 imaginary
+constexpr int VAD_HID = 128;     // encoder output / LSTM width
+constexpr int VAD_GATES = 512;   // i, f, g, o rows
+constexpr int VAD_TILE = 8;      // chunks per front-end workgroup
+struct VadWeights {
+  const float* basis_t;    // [256 taps][258 rows]
+  const float* conv_t[4];  // [cin * 3 + k][cout]
+  const float* conv_b[4];  // [cout]
+  const float* wih_t;      // [128][512]
+  const float* whh_t;      // [128][512]
+  const float* b_ih;       // [512]
+  const float* b_hh;       // [512]
+  const float* w_f;        // [128]
+  float b_f;
+};
+// chunk_off: n_clips + 1 prefix sums of ceil(n_samples / 512); clip b's chunk n
+// is row chunk_off[b] + n of pre ([total chunks][512]) and of probs.
+// Front end: STFT magnitude, the four convolutions and W_ih x + b_ih + b_hh of
+// every chunk of every clip (max_chunks = the longest clip's chunk count).
+void vad_frontend_launch(const VadWeights& w, const float* const* pcm, const int* n_samples,
+                         const int* chunk_off, int n_clips, int max_chunks, float* pre,
+                         hipStream_t st);
+// Recurrence + head: one workgroup per clip, h = c = 0 at its first chunk.
+void vad_lstm_launch(const VadWeights& w, const float* pre, const int* chunk_off, int n_clips,
+                     float* probs, hipStream_t st);
+
 }  // namespace mwx

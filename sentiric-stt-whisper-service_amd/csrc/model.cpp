@@ -330,13 +330,13 @@ bool read_model_file(const char* path, ModelFile& mf) {
 // ---------------------------------------------------------------------------
 // synthetic model writer
 // ---------------------------------------------------------------------------
-static uint64_t splitmix64(uint64_t x) {
+uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
   return x ^ (x >> 31);
 }
-static uint64_t fnv1a64(const std::string& s) {
+uint64_t fnv1a64(const std::string& s) {
   uint64_t h = 0xcbf29ce484222325ull;
   for (unsigned char c : s) {
     h ^= c;

@@ -1,0 +1,547 @@
+// Voice-activity detection: the model file (reader and seeded writer), the
+// VAD context and the mwx_vad_* entry points of include/mwx.h. The kernels are
+// in k_vad.hip; the network and the file layout are written down in
+// INTEGRATION.md ("VAD model").
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "common.h"
+#include "kernels.h"
+
+#define HIPC(x)                                                                        \
+  do {                                                                                 \
+    hipError_t e_ = (x);                                                               \
+    if (e_ != hipSuccess) {                                                            \
+      MWX_LOG_ERROR("mwx: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, \
+                    __LINE__);                                                         \
+      throw std::runtime_error("hip");                                                 \
+    }                                                                                  \
+  } while (0)
+
+namespace mwx {
+namespace {
+
+constexpr uint32_t kGgmlMagic = 0x67676d6c;  // "ggml"
+const char* const kVadType = "silero-16k";
+const int32_t kVadVersion[3] = {5, 0, 0};
+constexpr int kLayers = 4;
+const int32_t kEncIn[kLayers] = {129, 128, 64, 64};
+const int32_t kEncOut[kLayers] = {128, 64, 64, 128};
+const int32_t kEncKernel[kLayers] = {3, 3, 3, 3};
+
+struct VadTensorSpec {
+  std::string name;
+  std::vector<int64_t> shape;  // outermost first
+  int type;                    // the synthetic writer's type
+  float gain;                  // uniform in +-gain / sqrt(fan_in); 0 = the STFT basis
+  int fan_in;
+};
+
+// Every tensor of the file, in file order.
+std::vector<VadTensorSpec> vad_tensor_specs() {
+  std::vector<VadTensorSpec> v;
+  v.push_back({"_model.stft.forward_basis_buffer", {2 * VAD_BINS, VAD_NFFT}, GGML_F16, 0.0f, 1});
+  for (int l = 0; l < kLayers; ++l) {
+    const std::string p = "_model.encoder." + std::to_string(l) + ".reparam_conv.";
+    const int fan = kEncIn[l] * kEncKernel[l];
+    v.push_back({p + "weight", {kEncOut[l], kEncIn[l], kEncKernel[l]}, GGML_F16, 2.0f, fan});
+    v.push_back({p + "bias", {kEncOut[l]}, GGML_F32, 2.0f, fan});
+  }
+  const std::string r = "_model.decoder.rnn.";
+  v.push_back({r + "weight_ih", {VAD_GATES, VAD_HID}, GGML_F32, 3.0f, VAD_HID});
+  v.push_back({r + "weight_hh", {VAD_GATES, VAD_HID}, GGML_F32, 3.0f, VAD_HID});
+  v.push_back({r + "bias_ih", {VAD_GATES}, GGML_F32, 3.0f, VAD_HID});
+  v.push_back({r + "bias_hh", {VAD_GATES}, GGML_F32, 3.0f, VAD_HID});
+  v.push_back({"_model.decoder.decoder.2.weight", {1, VAD_HID, 1}, GGML_F32, 16.0f, VAD_HID});
+  v.push_back({"_model.decoder.decoder.2.bias", {1}, GGML_F32, 16.0f, VAD_HID});
+  return v;
+}
+
+// ---- reader -----------------------------------------------------------------
+struct Cursor {
+  const std::vector<uint8_t>& b;
+  size_t pos = 0;
+  bool take(void* dst, size_t n) {
+    if (n > b.size() - pos) return false;
+    memcpy(dst, b.data() + pos, n);
+    pos += n;
+    return true;
+  }
+  bool i32(int32_t& v) { return take(&v, 4); }
+};
+
+// Reads the file into f32 tensors keyed by name. false (logged) on any error.
+bool read_vad_file(const char* path, std::map<std::string, std::vector<float>>& out) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) {
+    MWX_LOG_ERROR("mwx_vad: cannot open '%s'\n", path);
+    return false;
+  }
+  const std::vector<uint8_t> bytes((std::istreambuf_iterator<char>(f)),
+                                   std::istreambuf_iterator<char>());
+  Cursor c{bytes};
+  auto truncated = [&](const char* what) {
+    MWX_LOG_ERROR("mwx_vad: '%s' is truncated (%s)\n", path, what);
+    return false;
+  };
+  uint32_t magic = 0;
+  if (!c.take(&magic, 4)) return truncated("magic");
+  if (magic != kGgmlMagic) {
+    MWX_LOG_ERROR("mwx_vad: '%s' has a bad magic %08x\n", path, magic);
+    return false;
+  }
+  int32_t len = 0;
+  if (!c.i32(len)) return truncated("model type");
+  if (len < 0 || (size_t)len > bytes.size() - c.pos) return truncated("model type");
+  std::string type(len, '\0');
+  c.take(&type[0], len);
+  if (type != kVadType) {
+    MWX_LOG_ERROR("mwx_vad: model type '%s' is not '%s'\n", type.c_str(), kVadType);
+    return false;
+  }
+  int32_t version[3];
+  if (!c.take(version, sizeof version)) return truncated("version");
+  // hyper-parameters: only the shape of INTEGRATION.md is supported
+  int32_t hp[1 + 3 * kLayers + 4];
+  if (!c.take(hp, sizeof hp)) return truncated("hyper-parameters");
+  bool ok = hp[0] == kLayers;
+  for (int l = 0; ok && l < kLayers; ++l)
+    ok = hp[1 + l] == kEncIn[l] && hp[1 + kLayers + l] == kEncOut[l] &&
+         hp[1 + 2 * kLayers + l] == kEncKernel[l];
+  const int32_t* tail = hp + 1 + 3 * kLayers;
+  ok = ok && tail[0] == VAD_HID && tail[1] == VAD_HID && tail[2] == VAD_HID && tail[3] == 1;
+  if (!ok) {
+    MWX_LOG_ERROR("mwx_vad: '%s' has unsupported hyper-parameters (expected 4 encoder layers "
+                  "129-128-64-64-128, kernel 3, LSTM 128/128, final conv 128 -> 1)\n", path);
+    return false;
+  }
+  std::map<std::string, VadTensorSpec> want;
+  for (auto& s : vad_tensor_specs()) want[s.name] = s;
+  while (c.pos < bytes.size()) {
+    int32_t nd = 0, nlen = 0, ttype = 0;
+    if (!c.i32(nd) || !c.i32(nlen) || !c.i32(ttype)) return truncated("tensor header");
+    if (nd < 1 || nd > 4 || nlen < 0 || nlen > 256) {
+      MWX_LOG_ERROR("mwx_vad: '%s' has a malformed tensor header\n", path);
+      return false;
+    }
+    std::vector<int64_t> shape(nd);
+    for (int i = 0; i < nd; ++i) {
+      int32_t d = 0;
+      if (!c.i32(d)) return truncated("tensor dims");
+      shape[nd - 1 - i] = d;  // file order is ggml's: innermost first
+    }
+    std::string name(nlen, '\0');
+    if (!c.take(&name[0], nlen)) return truncated("tensor name");
+    auto it = want.find(name);
+    if (it == want.end()) {
+      MWX_LOG_ERROR("mwx_vad: unknown tensor '%s'\n", name.c_str());
+      return false;
+    }
+    if (shape != it->second.shape) {
+      MWX_LOG_ERROR("mwx_vad: tensor '%s' has the wrong shape\n", name.c_str());
+      return false;
+    }
+    if (ttype != GGML_F32 && ttype != GGML_F16) {
+      MWX_LOG_ERROR("mwx_vad: tensor '%s' has type %d (f32 or f16 expected)\n", name.c_str(),
+                    ttype);
+      return false;
+    }
+    int64_t n = 1;
+    for (auto d : shape) n *= d;
+    const size_t esz = ttype == GGML_F32 ? 4 : 2;
+    if ((size_t)n * esz > bytes.size() - c.pos) return truncated(name.c_str());
+    std::vector<float> v((size_t)n);
+    if (ttype == GGML_F32) {
+      memcpy(v.data(), bytes.data() + c.pos, (size_t)n * 4);
+    } else {
+      for (int64_t i = 0; i < n; ++i) {
+        uint16_t h;
+        memcpy(&h, bytes.data() + c.pos + 2 * (size_t)i, 2);
+        v[(size_t)i] = f16_to_f32(h);
+      }
+    }
+    c.pos += (size_t)n * esz;
+    out[name] = std::move(v);
+  }
+  for (auto& kv : want)
+    if (!out.count(kv.first)) {
+      MWX_LOG_ERROR("mwx_vad: '%s' lacks tensor '%s'\n", path, kv.first.c_str());
+      return false;
+    }
+  return true;
+}
+
+// grow-only device buffer of the VAD context; a fresh allocation is zeroed on
+// the context's stream (never the null stream, which that stream does not
+// wait for). The stream is idle when a buffer grows: every call ends with a
+// synchronization.
+struct VBuf {
+  void* p = nullptr;
+  size_t n = 0;
+  void* get(size_t bytes, hipStream_t st) {
+    if (bytes > n) {
+      std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+      if (p) (void)hipFree(p);
+      p = nullptr;
+      n = 0;
+      HIPC(hipMalloc(&p, bytes));
+      n = bytes;
+      HIPC(hipMemsetAsync(p, 0, bytes, st));
+    }
+    return p;
+  }
+  void release() {
+    std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+  }
+};
+struct PinBuf {  // grow-only pinned host buffer
+  void* p = nullptr;
+  size_t n = 0;
+  void* get(size_t bytes) {
+    if (bytes > n) {
+      std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+      if (p) (void)hipHostFree(p);
+      p = nullptr;
+      n = 0;
+      HIPC(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+      n = bytes;
+    }
+    return p;
+  }
+  void release() {
+    std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    n = 0;
+  }
+};
+
+// (as driver.inc: plain host memory is unknown to HIP and reports an error)
+bool vad_is_device_ptr(const void* p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice;
+}
+
+}  // namespace
+}  // namespace mwx
+
+struct mwx_vad_context {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  bool timed = false;
+  float* d_weights = nullptr;
+  mwx::VadWeights w{};
+  mwx::VBuf d_pcm, d_pre, d_probs, d_meta;
+  mwx::PinBuf h_meta, h_probs;
+  std::vector<float> probs;  // mwx_vad_probs
+};
+
+namespace mwx {
+namespace {
+
+void vad_destroy(mwx_vad_context* v) {
+  if (!v) return;
+  (void)hipSetDevice(v->device);
+  if (v->stream) (void)hipStreamSynchronize(v->stream);
+  v->d_pcm.release();
+  v->d_pre.release();
+  v->d_probs.release();
+  v->d_meta.release();
+  v->h_meta.release();
+  v->h_probs.release();
+  {
+    std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+    if (v->d_weights) (void)hipFree(v->d_weights);
+  }
+  for (auto& e : v->ev)
+    if (e) (void)hipEventDestroy(e);
+  if (v->stream) (void)hipStreamDestroy(v->stream);
+  delete v;
+}
+
+// Weights to the device, transposed so that the output row is contiguous.
+void vad_upload(mwx_vad_context* v, std::map<std::string, std::vector<float>>& t) {
+  std::vector<float> host;
+  auto reserve = [&](size_t n) {
+    const size_t at = host.size();
+    host.resize(at + (n + 3) / 4 * 4, 0.0f);  // 16-byte aligned pieces
+    return at;
+  };
+  const int rows = 2 * VAD_BINS;
+  const auto& basis = t["_model.stft.forward_basis_buffer"];
+  const size_t o_basis = reserve((size_t)rows * VAD_NFFT);
+  for (int r = 0; r < rows; ++r)
+    for (int k = 0; k < VAD_NFFT; ++k) host[o_basis + (size_t)k * rows + r] = basis[(size_t)r * VAD_NFFT + k];
+  size_t o_conv[kLayers], o_bias[kLayers];
+  for (int l = 0; l < kLayers; ++l) {
+    const std::string p = "_model.encoder." + std::to_string(l) + ".reparam_conv.";
+    const auto& wt = t[p + "weight"];  // [out][in][3]
+    const int co = kEncOut[l], ci = kEncIn[l];
+    o_conv[l] = reserve((size_t)co * ci * 3);
+    for (int o = 0; o < co; ++o)
+      for (int i = 0; i < ci * 3; ++i) host[o_conv[l] + (size_t)i * co + o] = wt[(size_t)o * ci * 3 + i];
+    o_bias[l] = reserve(co);
+    memcpy(&host[o_bias[l]], t[p + "bias"].data(), (size_t)co * 4);
+  }
+  auto transposed_gates = [&](const std::vector<float>& wt) {  // [512][128] -> [128][512]
+    const size_t at = reserve((size_t)VAD_GATES * VAD_HID);
+    for (int j = 0; j < VAD_GATES; ++j)
+      for (int k = 0; k < VAD_HID; ++k) host[at + (size_t)k * VAD_GATES + j] = wt[(size_t)j * VAD_HID + k];
+    return at;
+  };
+  const size_t o_ih = transposed_gates(t["_model.decoder.rnn.weight_ih"]);
+  const size_t o_hh = transposed_gates(t["_model.decoder.rnn.weight_hh"]);
+  auto plain = [&](const std::vector<float>& x) {
+    const size_t at = reserve(x.size());
+    memcpy(&host[at], x.data(), x.size() * 4);
+    return at;
+  };
+  const size_t o_bih = plain(t["_model.decoder.rnn.bias_ih"]);
+  const size_t o_bhh = plain(t["_model.decoder.rnn.bias_hh"]);
+  const size_t o_wf = plain(t["_model.decoder.decoder.2.weight"]);
+  {
+    std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+    HIPC(hipMalloc((void**)&v->d_weights, host.size() * 4));
+  }
+  HIPC(hipMemcpyAsync(v->d_weights, host.data(), host.size() * 4, hipMemcpyHostToDevice, v->stream));
+  HIPC(hipStreamSynchronize(v->stream));
+  const float* d = v->d_weights;
+  v->w.basis_t = d + o_basis;
+  for (int l = 0; l < kLayers; ++l) {
+    v->w.conv_t[l] = d + o_conv[l];
+    v->w.conv_b[l] = d + o_bias[l];
+  }
+  v->w.wih_t = d + o_ih;
+  v->w.whh_t = d + o_hh;
+  v->w.b_ih = d + o_bih;
+  v->w.b_hh = d + o_bhh;
+  v->w.w_f = d + o_wf;
+  v->w.b_f = t["_model.decoder.decoder.2.bias"][0];
+}
+
+int vad_run(mwx_vad_context* v, const float* const* samples, const int* n_samples, int n_clips,
+            float* probs_out, const int* probs_offset) {
+  HIPC(hipSetDevice(v->device));
+  v->timed = false;
+  // chunk prefix sums; host clips are staged back to back in d_pcm
+  std::vector<int> off((size_t)n_clips + 1, 0);
+  std::vector<size_t> stage((size_t)n_clips, 0);
+  std::vector<char> on_device((size_t)n_clips, 0);
+  size_t stage_floats = 0;
+  int max_chunks = 0;
+  for (int b = 0; b < n_clips; ++b) {
+    if (n_samples[b] < 0 || (n_samples[b] > 0 && !samples[b])) return -2;
+    const int nc = mwx_vad_n_chunks(n_samples[b]);
+    if ((long)off[b] + nc > 0x7fffffffL) return -3;
+    off[b + 1] = off[b] + nc;
+    max_chunks = std::max(max_chunks, nc);
+    if (n_samples[b] > 0 && !(on_device[b] = vad_is_device_ptr(samples[b]))) {
+      stage[b] = stage_floats;
+      stage_floats += ((size_t)n_samples[b] + 3) / 4 * 4;
+    }
+  }
+  const int total = off[n_clips];
+  if (total == 0) return 0;
+  const long tiles = (max_chunks + VAD_TILE - 1) / VAD_TILE;  // front-end grid = clips x tiles
+  if (tiles * n_clips > 0x7fffffffL) return -3;
+  hipStream_t st = v->stream;
+  float* d_pcm = stage_floats ? (float*)v->d_pcm.get(stage_floats * 4, st) : nullptr;
+  // meta: [clip pointers][n_samples][chunk_off]
+  const size_t m_ptr = 0, m_ns = m_ptr + (size_t)n_clips * 8, m_off = m_ns + (size_t)n_clips * 4;
+  const size_t m_bytes = m_off + ((size_t)n_clips + 1) * 4;
+  char* hm = (char*)v->h_meta.get(m_bytes);
+  char* dm = (char*)v->d_meta.get(m_bytes, st);
+  for (int b = 0; b < n_clips; ++b) {
+    const float* p = samples[b];
+    if (n_samples[b] > 0 && !on_device[b]) {
+      HIPC(hipMemcpyAsync(d_pcm + stage[b], samples[b], (size_t)n_samples[b] * 4,
+                          hipMemcpyHostToDevice, st));
+      p = d_pcm + stage[b];
+    }
+    memcpy(hm + m_ptr + (size_t)b * 8, &p, 8);
+  }
+  memcpy(hm + m_ns, n_samples, (size_t)n_clips * 4);
+  memcpy(hm + m_off, off.data(), ((size_t)n_clips + 1) * 4);
+  HIPC(hipMemcpyAsync(dm, hm, m_bytes, hipMemcpyHostToDevice, st));
+  float* d_pre = (float*)v->d_pre.get((size_t)total * VAD_GATES * 4, st);
+  float* d_probs = (float*)v->d_probs.get((size_t)total * 4, st);
+  float* h_probs = (float*)v->h_probs.get((size_t)total * 4);
+  const float* const* d_ptrs = (const float* const*)(dm + m_ptr);
+  const int* d_ns = (const int*)(dm + m_ns);
+  const int* d_off = (const int*)(dm + m_off);
+  HIPC(hipEventRecord(v->ev[0], st));
+  vad_frontend_launch(v->w, d_ptrs, d_ns, d_off, n_clips, max_chunks, d_pre, st);
+  HIPC(hipEventRecord(v->ev[1], st));
+  vad_lstm_launch(v->w, d_pre, d_off, n_clips, d_probs, st);
+  HIPC(hipEventRecord(v->ev[2], st));
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(h_probs, d_probs, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  v->timed = true;
+  for (int b = 0; b < n_clips; ++b)
+    if (off[b + 1] > off[b])
+      memcpy(probs_out + probs_offset[b], h_probs + off[b], (size_t)(off[b + 1] - off[b]) * 4);
+  return 0;
+}
+
+}  // namespace
+}  // namespace mwx
+
+extern "C" {
+
+struct mwx_vad_context_params mwx_vad_default_context_params(void) {
+  mwx_vad_context_params p;
+  p.n_threads = 4;
+  p.use_gpu = true;
+  p.gpu_device = 0;
+  return p;
+}
+
+struct mwx_vad_context* mwx_vad_init_from_file_with_params(const char* path_model,
+                                                           struct mwx_vad_context_params params) {
+  if (!path_model) return nullptr;
+  if (!params.use_gpu) {
+    MWX_LOG_ERROR("mwx_vad: use_gpu = false is not supported (there is no CPU path)\n");
+    return nullptr;
+  }
+  std::map<std::string, std::vector<float>> tensors;
+  if (!mwx::read_vad_file(path_model, tensors)) return nullptr;
+  mwx_vad_context* v = new mwx_vad_context();
+  v->device = params.gpu_device;
+  try {
+    HIPC(hipSetDevice(v->device));
+    HIPC(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
+    for (auto& e : v->ev) HIPC(hipEventCreate(&e));
+    mwx::vad_upload(v, tensors);
+  } catch (const std::exception&) {
+    mwx::vad_destroy(v);
+    return nullptr;
+  }
+  return v;
+}
+
+void mwx_vad_free(struct mwx_vad_context* vctx) { mwx::vad_destroy(vctx); }
+
+int mwx_vad_n_chunks(int n_samples) {
+  return n_samples <= 0 ? 0 : (int)(((long)n_samples + mwx::VAD_CHUNK - 1) / mwx::VAD_CHUNK);
+}
+
+int mwx_vad_detect_speech_batch(struct mwx_vad_context* vctx, const float* const* samples,
+                                const int* n_samples, int n_clips, float* probs_out,
+                                const int* probs_offset) {
+  if (!vctx || n_clips < 0) return -1;
+  if (n_clips == 0) return 0;
+  if (!samples || !n_samples || !probs_out || !probs_offset) return -1;
+  try {
+    return mwx::vad_run(vctx, samples, n_samples, n_clips, probs_out, probs_offset);
+  } catch (const std::exception&) {
+    return -4;
+  }
+}
+
+bool mwx_vad_detect_speech(struct mwx_vad_context* vctx, const float* samples, int n_samples) {
+  if (!vctx || n_samples < 0 || (n_samples > 0 && !samples)) return false;
+  std::vector<float> out((size_t)mwx_vad_n_chunks(n_samples));
+  float dummy = 0.0f;
+  const int zero = 0;
+  const int rc = mwx_vad_detect_speech_batch(vctx, &samples, &n_samples, 1,
+                                             out.empty() ? &dummy : out.data(), &zero);
+  if (rc != 0) return false;
+  vctx->probs = std::move(out);
+  return true;
+}
+
+int mwx_vad_n_probs(struct mwx_vad_context* vctx) { return vctx ? (int)vctx->probs.size() : 0; }
+
+const float* mwx_vad_probs(struct mwx_vad_context* vctx) {
+  return vctx && !vctx->probs.empty() ? vctx->probs.data() : nullptr;
+}
+
+int mwx_vad_last_kernel_ms(struct mwx_vad_context* vctx, float* frontend_ms, float* lstm_ms) {
+  if (!vctx || !vctx->timed) return -1;
+  float a = 0.0f, b = 0.0f;
+  if (hipEventElapsedTime(&a, vctx->ev[0], vctx->ev[1]) != hipSuccess ||
+      hipEventElapsedTime(&b, vctx->ev[1], vctx->ev[2]) != hipSuccess)
+    return -1;
+  if (frontend_ms) *frontend_ms = a;
+  if (lstm_ms) *lstm_ms = b;
+  return 0;
+}
+
+// ---- synthetic writer -------------------------------------------------------
+int mwx_write_synthetic_vad_model(const char* path, uint64_t seed) {
+  using namespace mwx;
+  if (!path) return -1;
+  std::ofstream f(path, std::ios::binary);
+  if (!f) {
+    MWX_LOG_ERROR("mwx_write_synthetic_vad_model: cannot open '%s'\n", path);
+    return -1;
+  }
+  auto put = [&](const void* p, size_t n) { f.write(reinterpret_cast<const char*>(p), (std::streamsize)n); };
+  auto put32 = [&](int32_t v) { put(&v, 4); };
+  put(&kGgmlMagic, 4);
+  put32((int32_t)strlen(kVadType));
+  put(kVadType, strlen(kVadType));
+  put(kVadVersion, sizeof kVadVersion);
+  put32(kLayers);
+  put(kEncIn, sizeof kEncIn);
+  put(kEncOut, sizeof kEncOut);
+  put(kEncKernel, sizeof kEncKernel);
+  put32(VAD_HID);  // lstm_input
+  put32(VAD_HID);  // lstm_hidden
+  put32(VAD_HID);  // final_conv_in
+  put32(1);        // final_conv_out
+  const double two_pi = 6.283185307179586476925286766559;
+  for (const auto& s : vad_tensor_specs()) {
+    put32((int32_t)s.shape.size());
+    put32((int32_t)s.name.size());
+    put32(s.type);
+    for (int i = (int)s.shape.size() - 1; i >= 0; --i) put32((int32_t)s.shape[i]);
+    put(s.name.data(), s.name.size());
+    int64_t n = 1;
+    for (auto d : s.shape) n *= d;
+    const uint64_t key = fnv1a64(s.name) ^ seed;
+    const float bound = s.gain / std::sqrt((float)s.fan_in);
+    for (int64_t i = 0; i < n; ++i) {
+      float v;
+      if (s.gain == 0.0f) {
+        // Hann-windowed DFT: rows k < 129 cos, the rest -sin; periodic window
+        const int row = (int)(i / VAD_NFFT), t = (int)(i % VAD_NFFT);
+        const int k = row % VAD_BINS;
+        const double win = 0.5 - 0.5 * std::cos(two_pi * t / VAD_NFFT);
+        const double ang = two_pi * (double)((k * t) % VAD_NFFT) / VAD_NFFT;
+        v = (float)((row < VAD_BINS ? std::cos(ang) : -std::sin(ang)) * win);
+      } else {
+        const uint64_t r = splitmix64(key + (uint64_t)i * 0xD1B54A32D192ED03ull);
+        const float u = (float)((double)(r >> 40) * (1.0 / 8388608.0) - 1.0);
+        v = bound * u;
+      }
+      if (s.type == GGML_F32) {
+        put(&v, 4);
+      } else {
+        const uint16_t h = f32_to_f16(v);
+        put(&h, 2);
+      }
+    }
+  }
+  f.close();
+  return f ? 0 : -1;
+}
+
+}  // extern "C"

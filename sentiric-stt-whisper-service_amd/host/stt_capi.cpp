@@ -153,6 +153,62 @@ void* mwx_stt_new_ex(const char* model_dir, const char* model_filename, int para
   }
 }
 
+// As mwx_stt_new_ex, with the VAD speech gate (Settings::enable_vad,
+// vad_model_filename under model_dir, vad_threshold).
+void* mwx_stt_new_vad(const char* model_dir, const char* model_filename, int parallel_requests,
+                      int queue_timeout_ms, int beam_size, const char* language, int vad_ms_min,
+                      int gpu_device, int max_batch, int batch_window_us,
+                      int stream_buffer_samples, int enable_vad, const char* vad_model_filename,
+                      float vad_threshold) {
+  Settings s;
+  s.model_dir = model_dir;
+  s.model_filename = model_filename;
+  s.parallel_requests = parallel_requests;
+  s.request_queue_timeout_ms = queue_timeout_ms;
+  s.beam_size = beam_size;
+  s.language = language;
+  s.vad_ms_min_duration = vad_ms_min;
+  s.gpu_device = gpu_device;
+  s.max_batch = max_batch;
+  s.batch_window_us = batch_window_us;
+  s.stream_buffer_samples = stream_buffer_samples;
+  s.enable_vad = enable_vad != 0;
+  if (vad_model_filename) s.vad_model_filename = vad_model_filename;
+  s.vad_threshold = vad_threshold;
+  try {
+    return new SttEngine(s);
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "SttEngine: %s\n", e.what());
+    return nullptr;
+  }
+}
+
+// SttEngine::transcribe_batch over n_clips f32 clips at 16 kHz: a JSON list
+// with one result list per clip (as mwx_stt_transcribe_pcm16 writes one).
+// Return codes as mwx_stt_transcribe_pcm16.
+int mwx_stt_transcribe_batch_f32(void* eng, const float* const* pcm, const int* n, int n_clips,
+                                 const char* language, int beam_size, float temperature, char* out,
+                                 int cap) {
+  RequestOptions o;
+  o.language = language ? language : "";
+  o.beam_size = beam_size;
+  o.temperature = temperature;
+  try {
+    std::vector<std::vector<float>> clips;
+    for (int b = 0; b < n_clips; ++b) clips.emplace_back(pcm[b], pcm[b] + n[b]);
+    const auto rs = static_cast<SttEngine*>(eng)->transcribe_batch(clips, o);
+    std::string j = "[";
+    for (size_t b = 0; b < rs.size(); ++b) j += (b ? "," : "") + to_json(rs[b]);
+    j += "]";
+    const int r = emit(j, out, cap);
+    return r < -1 ? r - 2 : r;
+  } catch (const EngineBusyException&) {
+    return -2;
+  } catch (...) {
+    return -1;
+  }
+}
+
 // StreamSession over an engine: feed one chunk (len 0 = end of speech);
 // returns the events as JSON (strings hex-encoded) like mwx_stt_transcribe_pcm16.
 // If `cap` is too small the chunk is still consumed: the events are kept and

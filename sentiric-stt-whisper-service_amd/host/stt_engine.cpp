@@ -9,6 +9,18 @@
 
 #include "text_filters.h"
 
+// The VAD entry points are bound weakly: a library without them (an older
+// libmwx, the CPU stub of the sanitizer builds) still links, and enable_vad
+// then behaves as "the VAD model failed to load" (gate open).
+#pragma weak mwx_vad_default_context_params
+#pragma weak mwx_vad_init_from_file_with_params
+#pragma weak mwx_vad_free
+#pragma weak mwx_vad_detect_speech
+#pragma weak mwx_vad_n_probs
+#pragma weak mwx_vad_probs
+#pragma weak mwx_vad_n_chunks
+#pragma weak mwx_vad_detect_speech_batch
+
 namespace mwx_host {
 
 namespace {
@@ -93,6 +105,21 @@ SttEngine::SttEngine(const Settings& settings) : settings_(settings) {
   aux_state_ = mwx_init_state(ctx_);
   if (!aux_state_) throw std::runtime_error("Whisper state initialization failed");
   all_states_.push_back(aux_state_);
+  // src/stt_engine.cpp:44-55: a VAD model that does not load is logged and the
+  // engine carries on without the gate
+  if (settings_.enable_vad) {
+    const std::string vad_path = settings_.model_dir + "/" + settings_.vad_model_filename;
+    if (mwx_vad_default_context_params && mwx_vad_init_from_file_with_params &&
+        mwx_vad_detect_speech && mwx_vad_n_probs && mwx_vad_probs && mwx_vad_free) {
+      mwx_vad_context_params vp = mwx_vad_default_context_params();
+      vp.n_threads = settings_.n_threads;
+      vp.use_gpu = true;
+      vp.gpu_device = settings_.gpu_device;
+      vad_ctx_ = mwx_vad_init_from_file_with_params(vad_path.c_str(), vp);
+    }
+    if (!vad_ctx_)
+      std::fprintf(stderr, "SttEngine: VAD model %s not loaded, VAD disabled\n", vad_path.c_str());
+  }
   const int pool = std::max(1, settings_.parallel_requests);
   if (settings_.max_batch > 1) {
     // one batcher thread per pool slot, each with its own max_batch states
@@ -124,6 +151,7 @@ SttEngine::~SttEngine() {
   q_cv_.notify_all();
   for (auto& t : batchers_) t.join();
   for (mwx_state* st : all_states_) mwx_free_state(st);
+  if (vad_ctx_) mwx_vad_free(vad_ctx_);
   if (ctx_) mwx_free(ctx_);
 }
 
@@ -392,6 +420,34 @@ std::vector<TranscriptionResult> SttEngine::collect(mwx_state* state, const std:
   return results;
 }
 
+bool SttEngine::is_speech_detected(const float* pcm, size_t n_samples) {
+  if (!vad_ctx_) return true;
+  std::lock_guard<std::mutex> lock(vad_mutex_);
+  if (!mwx_vad_detect_speech(vad_ctx_, pcm, static_cast<int>(n_samples))) return true;
+  const int n = mwx_vad_n_probs(vad_ctx_);
+  const float* probs = mwx_vad_probs(vad_ctx_);
+  for (int i = 0; i < n; ++i)
+    if (probs[i] >= settings_.vad_threshold) return true;
+  return false;
+}
+
+TranscriptionResult SttEngine::empty_result(size_t pcm_size) {
+  TranscriptionResult r;
+  r.text = "";
+  r.language = "unknown";
+  r.prob = 0.0f;
+  r.t0 = 0;
+  r.t1 = static_cast<int64_t>(pcm_size / 16.0);
+  r.speaker_turn_next = false;
+  r.token_count = 0;
+  // extract_prosody(nullptr, 0, ...): src/prosody_extractor.cpp:35-48
+  r.affective.gender_proxy = "?";
+  r.affective.emotion_proxy = "neutral";
+  r.affective.speaker_vec.assign(8, 0.0f);
+  r.speaker_id = "unknown";
+  return r;
+}
+
 std::vector<TranscriptionResult> SttEngine::transcribe(const std::vector<float>& pcmf32,
                                                        int input_sample_rate,
                                                        const RequestOptions& options,
@@ -412,6 +468,12 @@ std::vector<TranscriptionResult> SttEngine::transcribe(const std::vector<float>&
   if (pcm_size < min_samples) {
     if (out_metrics) *out_metrics = {0.0, 0.0, 0};
     return {};
+  }
+  // src/stt_engine.cpp:169-194: silence never reaches Whisper
+  if (settings_.enable_vad && !is_speech_detected(pcm.data(), pcm_size)) {
+    if (out_metrics)
+      *out_metrics = {0.0, ms_between(t_start, std::chrono::steady_clock::now()), 0};
+    return {empty_result(pcm_size)};
   }
   if (settings_.max_batch > 1) return transcribe_batched(pcm, options, out_metrics);
   StateGuard guard(*this);
@@ -458,31 +520,73 @@ std::vector<std::vector<TranscriptionResult>> SttEngine::transcribe_batch(
     const std::vector<std::vector<float>>& clips, const RequestOptions& options) {
   std::vector<std::vector<TranscriptionResult>> out(clips.size());
   if (!ctx_ || clips.empty()) return out;
+  const size_t min_samples = static_cast<size_t>((settings_.vad_ms_min_duration * 16000) / 1000);
+  // VAD gate: one batched pass over the clips that pass the minimum duration;
+  // a silent clip gets the empty result and is left out of the Whisper batch
+  std::vector<size_t> run;  // indices of the clips that go to mwx_full_batch
+  if (vad_ctx_ && mwx_vad_detect_speech_batch && mwx_vad_n_chunks) {
+    std::vector<size_t> gated;
+    std::vector<const float*> vptrs;
+    std::vector<int> vlens, voff;
+    int total = 0;
+    for (size_t b = 0; b < clips.size(); ++b) {
+      if (clips[b].size() < min_samples) {
+        run.push_back(b);  // as before: decoded with the batch, result dropped
+        continue;
+      }
+      gated.push_back(b);
+      vptrs.push_back(clips[b].data());
+      vlens.push_back(static_cast<int>(clips[b].size()));
+      voff.push_back(total);
+      total += mwx_vad_n_chunks(vlens.back());
+    }
+    std::vector<float> probs(static_cast<size_t>(std::max(total, 1)));
+    int rc = 0;
+    if (!gated.empty()) {
+      std::lock_guard<std::mutex> lock(vad_mutex_);
+      rc = mwx_vad_detect_speech_batch(vad_ctx_, vptrs.data(), vlens.data(),
+                                       static_cast<int>(gated.size()), probs.data(), voff.data());
+    }
+    for (size_t g = 0; g < gated.size(); ++g) {
+      bool speech = rc != 0;  // a failed call leaves the gate open
+      const int n = mwx_vad_n_chunks(vlens[g]);
+      for (int i = 0; i < n && !speech; ++i) speech = probs[voff[g] + i] >= settings_.vad_threshold;
+      if (speech)
+        run.push_back(gated[g]);
+      else
+        out[gated[g]] = {empty_result(clips[gated[g]].size())};
+    }
+    std::sort(run.begin(), run.end());
+  } else {
+    for (size_t b = 0; b < clips.size(); ++b) run.push_back(b);
+  }
+  if (run.empty()) return out;
   std::lock_guard<std::mutex> batch_lock(batch_mutex_);
-  while (batch_states_.size() < clips.size()) {
+  while (batch_states_.size() < run.size()) {
     mwx_state* st = mwx_init_state(ctx_);
     if (!st) return out;
     batch_states_.push_back(st);
     all_states_.push_back(st);
   }
-  std::vector<mwx_state*> states(batch_states_.begin(), batch_states_.begin() + clips.size());
+  std::vector<mwx_state*> states(batch_states_.begin(), batch_states_.begin() + run.size());
   std::vector<const float*> ptrs;
   std::vector<int> lens;
-  for (const auto& c : clips) {
-    ptrs.push_back(c.data());
-    lens.push_back(static_cast<int>(c.size()));
+  for (size_t b : run) {
+    ptrs.push_back(clips[b].data());
+    lens.push_back(static_cast<int>(clips[b].size()));
   }
   std::string lang;
   std::function<bool()> abort_fn = options.should_abort;
   const mwx_full_params p = make_params(options, lang, abort_fn);
   const int ret = mwx_full_batch(ctx_, states.data(), p, ptrs.data(), lens.data(),
-                                 static_cast<int>(clips.size()));
+                                 static_cast<int>(run.size()));
   if (ret == 0) {
-    const size_t min_samples = static_cast<size_t>((settings_.vad_ms_min_duration * 16000) / 1000);
-    for (size_t b = 0; b < clips.size(); ++b)
+    for (size_t i = 0; i < run.size(); ++i) {
+      const size_t b = run[i];
       if (clips[b].size() >= min_samples)
-        out[b] = collect(states[b], lang, clips[b].data(), clips[b].size(), options.prosody_opts,
+        out[b] = collect(states[i], lang, clips[b].data(), clips[b].size(), options.prosody_opts,
                          nullptr);
+    }
   }
   return out;
 }

@@ -12,8 +12,11 @@
 // speaker clustering (src/speaker_cluster.cpp, restated below), and
 // resampling of non-16 kHz input (resample_audio, :87-106, :138-145: on the
 // GPU by mwx_resample; the input is kept when resampling yields nothing, as
-// the reference keeps it when libsamplerate fails, :141). Out of scope
-// (SURVEY.md §8): VAD.
+// the reference keeps it when libsamplerate fails, :141), and the VAD speech
+// gate (is_speech_detected, :108-115, :169-194: on the GPU by mwx_vad_*; a clip
+// with no speech comes back as one empty result and never takes a state).
+// The gate's decision rule is this engine's own (deviation D6): any
+// chunk probability >= Settings::vad_threshold.
 #pragma once
 
 #include <atomic>
@@ -39,7 +42,11 @@ namespace mwx_host {
 struct Settings {
   std::string model_dir = "/models";
   std::string model_filename = "ggml-medium.bin";
-  bool enable_vad = false;  // VAD is out of scope: must stay false
+  // The reference defaults to true (src/config.h:30); off here so that an
+  // engine built without a VAD model file behaves as before.
+  bool enable_vad = false;
+  std::string vad_model_filename = "ggml-silero-vad.bin";  // src/config.h:25
+  float vad_threshold = 0.75f;                             // src/config.h:34
   int vad_ms_min_duration = 500;
   int n_threads = 4;
   int parallel_requests = 2;
@@ -189,6 +196,11 @@ class SttEngine {
   std::vector<float> resample_audio(const float* input, size_t input_size, int src_rate,
                                     int target_rate);
 
+  // src/stt_engine.cpp:108-115. True when there is no VAD context or the call
+  // failed (the gate stays open); otherwise true when at least one chunk
+  // probability is >= Settings::vad_threshold.
+  bool is_speech_detected(const float* pcm, size_t n_samples);
+
   // Batches run by the request batcher so far (max_batch > 1).
   long batches_run() const { return batches_run_.load(); }
 
@@ -226,8 +238,13 @@ class SttEngine {
                                            const float* pcm, size_t pcm_size,
                                            const ProsodyOptions& popts, int* token_count) const;
 
+  // the one result of a clip the VAD gate holds back (src/stt_engine.cpp:172-183)
+  static TranscriptionResult empty_result(size_t pcm_size);
+
   Settings settings_;
   mwx_context* ctx_ = nullptr;
+  mwx_vad_context* vad_ctx_ = nullptr;
+  std::mutex vad_mutex_;
   std::queue<mwx_state*> state_pool_;
   std::mutex pool_mutex_;
   std::condition_variable pool_cv_;

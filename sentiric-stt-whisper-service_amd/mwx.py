@@ -95,6 +95,11 @@ class FullParams(C.Structure):
     ]
 
 
+class VadContextParams(C.Structure):
+    """mwx_vad_context_params (whisper_vad_context_params)."""
+    _fields_ = [("n_threads", C.c_int), ("use_gpu", C.c_bool), ("gpu_device", C.c_int)]
+
+
 class ProsodyParams(C.Structure):
     """mwx_prosody_params = the reference's ProsodyOptions
     (src/prosody_extractor.h:21-27)."""
@@ -254,6 +259,27 @@ def lib() -> C.CDLL:
     L.mwx_prosody_batch_device.restype = C.c_int
     L.mwx_prosody_batch_device.argtypes = [P, P, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
                                            C.c_int, C.POINTER(ProsodyParams), C.c_void_p]
+    L.mwx_vad_default_context_params.restype = VadContextParams
+    L.mwx_vad_default_context_params.argtypes = []
+    L.mwx_vad_init_from_file_with_params.restype = P
+    L.mwx_vad_init_from_file_with_params.argtypes = [C.c_char_p, VadContextParams]
+    L.mwx_vad_free.restype = None
+    L.mwx_vad_free.argtypes = [P]
+    L.mwx_vad_detect_speech.restype = C.c_bool
+    L.mwx_vad_detect_speech.argtypes = [P, C.c_void_p, C.c_int]
+    L.mwx_vad_n_probs.restype = C.c_int
+    L.mwx_vad_n_probs.argtypes = [P]
+    L.mwx_vad_probs.restype = fpp
+    L.mwx_vad_probs.argtypes = [P]
+    L.mwx_vad_n_chunks.restype = C.c_int
+    L.mwx_vad_n_chunks.argtypes = [C.c_int]
+    L.mwx_vad_detect_speech_batch.restype = C.c_int
+    L.mwx_vad_detect_speech_batch.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int,
+                                              fpp, C.POINTER(C.c_int)]
+    L.mwx_vad_last_kernel_ms.restype = C.c_int
+    L.mwx_vad_last_kernel_ms.argtypes = [P, fpp, fpp]
+    L.mwx_write_synthetic_vad_model.restype = C.c_int
+    L.mwx_write_synthetic_vad_model.argtypes = [C.c_char_p, C.c_uint64]
     _lib = L
     return L
 
@@ -284,6 +310,13 @@ def write_synthetic_model(path: str, arch: str, wtype: int = GGML_F16, seed: int
     rc = lib().mwx_write_synthetic_model(path.encode(), arch.encode(), wtype, seed)
     if rc != 0:
         raise RuntimeError(f"mwx_write_synthetic_model failed ({rc})")
+
+
+def write_synthetic_vad_model(path: str, seed: int = 0) -> None:
+    """mwx_write_synthetic_vad_model: a seeded Silero-v5-shaped VAD model."""
+    rc = lib().mwx_write_synthetic_vad_model(path.encode(), seed)
+    if rc != 0:
+        raise RuntimeError(f"mwx_write_synthetic_vad_model failed ({rc})")
 
 
 def set_xattn_mfs(on: Optional[bool]) -> int:
@@ -761,6 +794,75 @@ class Context:
         c = cls(model_path, device, compute)
         c._hp = read_hparams(model_path)
         return c
+
+
+class VadContext:
+    """mwx_vad_context: one speech probability per 512-sample chunk of 16 kHz
+    f32 PCM. Clips may be numpy arrays or DevicePCM buffers (Context.upload) of
+    the same GPU. One call at a time per context."""
+
+    def __init__(self, model_path: str, device: int = 0):
+        L = lib()
+        vp = L.mwx_vad_default_context_params()
+        vp.gpu_device = device
+        self.vctx = L.mwx_vad_init_from_file_with_params(model_path.encode(), vp)
+        if not self.vctx:
+            raise RuntimeError(f"mwx_vad_init_from_file_with_params failed for {model_path}")
+
+    def close(self):
+        if self.vctx:
+            lib().mwx_vad_free(self.vctx)
+            self.vctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @staticmethod
+    def _clip(pcm):
+        """(keep-alive object, address, sample count)"""
+        if isinstance(pcm, DevicePCM):
+            return pcm, C.cast(pcm.ptr, C.c_void_p).value, pcm.n
+        a = np.ascontiguousarray(pcm, dtype=np.float32)
+        return a, a.ctypes.data, len(a)
+
+    def detect(self, pcm) -> np.ndarray:
+        """mwx_vad_detect_speech + mwx_vad_probs: the chunk probabilities."""
+        L = lib()
+        _keep, addr, n = self._clip(pcm)
+        if not L.mwx_vad_detect_speech(self.vctx, addr, n):
+            raise RuntimeError("mwx_vad_detect_speech failed")
+        k = L.mwx_vad_n_probs(self.vctx)
+        if k == 0:
+            return np.empty(0, np.float32)
+        return np.ctypeslib.as_array(L.mwx_vad_probs(self.vctx), shape=(k,)).copy()
+
+    def detect_batch(self, pcms) -> List[np.ndarray]:
+        """mwx_vad_detect_speech_batch: every clip in one pass."""
+        L = lib()
+        clips = [self._clip(p) for p in pcms]
+        n = len(clips)
+        if n == 0:
+            return []
+        counts = [L.mwx_vad_n_chunks(c[2]) for c in clips]
+        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        out = np.empty(max(1, int(offs[-1])), np.float32)
+        ptrs = (C.c_void_p * n)(*[c[1] for c in clips])
+        lens = (C.c_int * n)(*[c[2] for c in clips])
+        rc = L.mwx_vad_detect_speech_batch(self.vctx, ptrs, lens, n, fptr(out),
+                                           offs.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != 0:
+            raise RuntimeError(f"mwx_vad_detect_speech_batch failed ({rc})")
+        return [out[offs[i]:offs[i + 1]].copy() for i in range(n)]
+
+    def last_kernel_ms(self):
+        """(front end, recurrence + head) device milliseconds of the last call."""
+        a, b = C.c_float(), C.c_float()
+        if lib().mwx_vad_last_kernel_ms(self.vctx, C.byref(a), C.byref(b)) != 0:
+            raise RuntimeError("mwx_vad_last_kernel_ms: no timed call")
+        return a.value, b.value
 
 
 def read_hparams(path: str) -> List[int]:
