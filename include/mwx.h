@@ -30,7 +30,12 @@
  * mwx_write_synthetic_model writes a seeded model in the ggml .bin layout that
  * src/model_manager.cpp provisions (no real checkpoints exist offline).
  * The whisper_vad_* family (src/stt_engine.cpp:44-55, :108-115) maps to
- * mwx_vad_*: see the voice-activity section below.
+ * mwx_vad_*: see the voice-activity section below. whisper_vad_segments_* and
+ * whisper_full's params.vad map to mwx_vad_segments_*, mwx_vad_trim_batch and
+ * mwx_full_batch_trimmed ("VAD speech segments and silence trimming" below):
+ * segments, the gather of the speech into a dense buffer and the transcription
+ * of that buffer with times on the caller's timeline, all on the GPU with one
+ * upload of the audio. The segment rule is this project's definition.
  *
  * Conventions: plain C, no exceptions cross this boundary, all functions return
  * NULL / negative on failure (0 = success), strings returned by getters stay
@@ -353,6 +358,90 @@ int mwx_vad_detect_speech_batch(struct mwx_vad_context* vctx, const float* const
 /* Device time of the last call's two kernels (front end; recurrence + head)
  * in milliseconds, from HIP events on the context's stream. 0 on success. */
 int mwx_vad_last_kernel_ms(struct mwx_vad_context* vctx, float* frontend_ms, float* lstm_ms);
+
+/* --- VAD speech segments and silence trimming --------------------------------
+ *   mwx_vad_default_params             <- whisper_vad_default_params
+ *   mwx_vad_segments_from_probs        <- whisper_vad_segments_from_probs
+ *   mwx_vad_segments_from_samples      <- whisper_vad_segments_from_samples
+ *   mwx_vad_segments_n_segments        <- whisper_vad_segments_n_segments
+ *   mwx_vad_segments_get_segment_t0/t1 <- whisper_vad_segments_get_segment_t0/t1
+ *   mwx_vad_free_segments              <- whisper_vad_free_segments
+ *   mwx_vad_trim_batch + mwx_full_batch_trimmed  ~ whisper_full with params.vad
+ *
+ * The rule that turns chunk probabilities into segments is this project's
+ * definition (Silero's get_speech_timestamps restated; DESIGN.md deviation D7,
+ * written out in INTEGRATION.md "VAD speech segments"): parity with
+ * whisper.cpp's whisper_vad_segments_from_probs / whisper_vad is unpinned. It
+ * runs on the GPU (csrc/k_vad.hip, vad_segments_kernel) over the probabilities
+ * the network kernels left there. */
+struct mwx_vad_params {           /* whisper_vad_params: same names and defaults */
+  float threshold;                /* 0.5: p >= threshold is speech */
+  int min_speech_duration_ms;     /* 250 */
+  int min_silence_duration_ms;    /* 100 */
+  float max_speech_duration_s;    /* FLT_MAX */
+  int speech_pad_ms;              /* 30 */
+  float samples_overlap;          /* 0.1 s kept after a segment in the trimmed audio */
+};
+struct mwx_vad_params mwx_vad_default_params(void);
+
+/* NULL (with a logged reason) on invalid parameters (threshold outside (0, 1),
+ * a negative duration, max_speech_duration_s <= 0, samples_overlap < 0, NaN) or
+ * a device error. from_probs uses the probabilities and the clip length of the
+ * context's last mwx_vad_detect_speech; from_samples runs that call first. */
+struct mwx_vad_segments;
+struct mwx_vad_segments* mwx_vad_segments_from_probs(struct mwx_vad_context* vctx,
+                                                     struct mwx_vad_params params);
+struct mwx_vad_segments* mwx_vad_segments_from_samples(struct mwx_vad_context* vctx,
+                                                       struct mwx_vad_params params,
+                                                       const float* samples, int n_samples);
+int mwx_vad_segments_n_segments(struct mwx_vad_segments* segments);
+/* centiseconds = samples / 160.0f */
+float mwx_vad_segments_get_segment_t0(struct mwx_vad_segments* segments, int i_segment);
+float mwx_vad_segments_get_segment_t1(struct mwx_vad_segments* segments, int i_segment);
+void mwx_vad_free_segments(struct mwx_vad_segments* segments);
+
+/* Engine extension: VAD, segments and compaction of n_clips clips (host or
+ * device memory) in one pass. Host clips are uploaded once, for the VAD, and
+ * compacted from that copy; the speech of every clip (each segment followed by
+ * samples_overlap of audio, 0.1 s of zeros between pieces that are not adjacent)
+ * lands in one device buffer that the returned object owns. The object does not
+ * depend on vctx afterwards. NULL on invalid parameters or a device error. */
+struct mwx_vad_trimmed;
+struct mwx_vad_trimmed* mwx_vad_trim_batch(struct mwx_vad_context* vctx,
+                                           struct mwx_vad_params params,
+                                           const float* const* samples, const int* n_samples,
+                                           int n_clips);
+int mwx_vad_trimmed_n_clips(const struct mwx_vad_trimmed* t);
+int mwx_vad_trimmed_n_segments(const struct mwx_vad_trimmed* t, int clip);
+/* Segment i of the clip in samples of the caller's clip; 0, or < 0 out of range. */
+int mwx_vad_trimmed_segment(const struct mwx_vad_trimmed* t, int clip, int i, int64_t* s0,
+                            int64_t* s1);
+int64_t mwx_vad_trimmed_n_samples(const struct mwx_vad_trimmed* t, int clip); /* compacted */
+/* Device pointer to the clip's compacted PCM (NULL when it has no samples). */
+const float* mwx_vad_trimmed_pcm(const struct mwx_vad_trimmed* t, int clip);
+/* A time of the compacted clip, in centiseconds, on the caller's timeline.
+ * is_end: the value ends something (t1) and maps to the end of the speech
+ * before a gap rather than to the start of the speech after it. A value < 0
+ * stays as it is. */
+int64_t mwx_vad_trimmed_map_time(const struct mwx_vad_trimmed* t, int clip, int64_t t_cs,
+                                 bool is_end);
+void mwx_vad_trimmed_free(struct mwx_vad_trimmed* t);
+/* Device time of the last mwx_vad_trim_batch's two kernels (segments;
+ * compaction) in milliseconds. 0 on success, -1 if nothing was compacted. */
+int mwx_vad_last_trim_kernel_ms(struct mwx_vad_context* vctx, float* segments_ms,
+                                float* compact_ms);
+
+/* As mwx_full_batch over trimmed audio: batch entry b is clip clip_index[b] of
+ * trimmed[b] (one object for the whole batch, or one single-clip object per
+ * queued request). A clip without segments is left out of the Whisper pass and
+ * its state ends with 0 segments; the others run through mwx_full_batch on
+ * their compacted device PCM, and every segment and token time stored in their
+ * states is then mapped, so the mwx_full_get_* getters return times of the
+ * caller's clip. An object of another device than ctx is an error. */
+int mwx_full_batch_trimmed(struct mwx_context* ctx, struct mwx_state* const* states,
+                           struct mwx_full_params params,
+                           const struct mwx_vad_trimmed* const* trimmed, const int* clip_index,
+                           int n_clips);
 
 /* --- vocabulary / model ------------------------------------------------- */
 const char* mwx_token_to_str(struct mwx_context* ctx, mwx_token token);

@@ -149,6 +149,22 @@ int mwx_test_xattn_mx(struct mwx_context* ctx, int R, int H, int n, int nq, cons
                       const uint8_t* k8, const uint8_t* ks, const uint8_t* v8, const uint8_t* vs,
                       float* o);
 
+/* vad_segments_kernel on caller-supplied probabilities: clip b has
+ * mwx_vad_n_chunks(n_samples[b]) of them at probs + probs_offset[b] and its own
+ * params[b]. Out: n_segments[b], compact_len[b], its segments as (start, end)
+ * pairs at segments + 2 * out_offset[b] and its pieces as (src, len, dst)
+ * triples at pieces + 3 * out_offset[b]; room for as many entries as the clip
+ * has chunks. Returns 0 or < 0. */
+int mwx_test_vad_segments(struct mwx_vad_context* vctx, const struct mwx_vad_params* params,
+                          const float* probs, const int* probs_offset, const int* n_samples,
+                          int n_clips, int* n_segments, int64_t* compact_len, int64_t* segments,
+                          int64_t* pieces, const int* out_offset);
+
+/* Copies a compacted clip of a trimmed batch to the host. Returns its sample
+ * count, or < 0 on bad arguments, cap too small or a device error. */
+int64_t mwx_test_vad_trimmed_pcm(const struct mwx_vad_trimmed* t, int clip, float* out,
+                                 int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1580,6 +1580,54 @@ int mwx_full_batch_pcm16(struct mwx_context* ctx, struct mwx_state* const* state
                         n_samples, n_clips, true);
 }
 
+// Trimmed audio (vad.cpp, mwx_vad_trim_batch) through the batched path: the
+// clips that have speech run on their compacted device PCM, then every stored
+// time moves from the compacted timeline to the caller's.
+int mwx_full_batch_trimmed(struct mwx_context* ctx, struct mwx_state* const* states,
+                           struct mwx_full_params params,
+                           const struct mwx_vad_trimmed* const* trimmed, const int* clip_index,
+                           int n_clips) {
+  if (!ctx || !states || !trimmed || !clip_index || n_clips <= 0) return -1;
+  std::vector<mwx_state*> run_states;
+  std::vector<const void*> ptrs;
+  std::vector<int> lens;
+  std::vector<const mwx_vad_trimmed::Clip*> run_clips;
+  for (int b = 0; b < n_clips; ++b) {
+    const mwx_vad_trimmed* t = trimmed[b];
+    if (!states[b] || !t || clip_index[b] < 0 || (size_t)clip_index[b] >= t->clips.size())
+      return -1;
+    if (t->device != ctx->c.device) {
+      MWX_LOG_ERROR("mwx_full_batch_trimmed: trimmed audio of device %d, context on device %d\n",
+                    t->device, ctx->c.device);
+      return -1;
+    }
+    if (t->clips[clip_index[b]].n_compact > 0x7fffffffLL) return -1;
+  }
+  for (int b = 0; b < n_clips; ++b) {
+    const mwx_vad_trimmed::Clip& c = trimmed[b]->clips[clip_index[b]];
+    states[b]->s.result_all.clear();
+    if (c.seg.empty() || c.n_compact <= 0) continue;
+    run_states.push_back(states[b]);
+    ptrs.push_back(trimmed[b]->d_pcm + c.off);
+    lens.push_back((int)c.n_compact);
+    run_clips.push_back(&c);
+  }
+  if (run_states.empty()) return 0;
+  const int rc = full_batch_any(ctx, run_states.data(), params, ptrs.data(), lens.data(),
+                                (int)run_states.size(), false);
+  if (rc != 0) return rc;
+  for (size_t r = 0; r < run_states.size(); ++r)
+    for (auto& sg : run_states[r]->s.result_all) {
+      sg.t0 = mwx::vad_map_time(*run_clips[r], sg.t0, false);
+      sg.t1 = mwx::vad_map_time(*run_clips[r], sg.t1, true);
+      for (auto& td : sg.tokens) {
+        td.t0 = mwx::vad_map_time(*run_clips[r], td.t0, false);
+        td.t1 = mwx::vad_map_time(*run_clips[r], td.t1, true);
+      }
+    }
+  return 0;
+}
+
 float* mwx_device_buffer(struct mwx_context* ctx, size_t n) {
   if (!ctx || n == 0) return nullptr;
   if (hipSetDevice(ctx->c.device) != hipSuccess) return nullptr;

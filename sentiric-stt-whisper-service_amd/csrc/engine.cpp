@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "vad_trim.h"
 
 #define HIPC(x)                                                                        \
   do {                                                                                 \

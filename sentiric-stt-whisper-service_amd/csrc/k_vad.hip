@@ -4,7 +4,7 @@
 // (src/stt_engine.cpp:108-115), which the reference runs on the CPU one clip
 // at a time.
 //
-// Two kernels:
+// Two kernels compute the probabilities:
 //   vad_frontend_kernel — everything that does not depend on the LSTM state,
 //     for every chunk of every clip of the call at once: reflect padding, the
 //     STFT magnitude, four kernel-3 convolutions with ReLU and the LSTM input
@@ -14,6 +14,11 @@
 //   vad_lstm_kernel — the 128-wide recurrence and the head, one workgroup per
 //     clip: 512 threads, thread j keeps row j of W_hh in registers for the
 //     whole clip, h is broadcast through LDS.
+//
+// Two more turn them into trimmed audio without leaving the device
+// (DESIGN.md D7): vad_segments_kernel (one wave per clip: the segment rule over
+// the probabilities, padding, the piece layout of the compacted clip) and
+// vad_compact_kernel (gathers the pieces of every clip into one dense buffer).
 //
 // All arithmetic is f32. Every output is one fixed chain of fmaf over its
 // inputs in index order, so a chunk's result does not depend on its slot in a
@@ -244,6 +249,178 @@ __global__ __launch_bounds__(VAD_GATES) void vad_lstm_kernel(
   }
 }
 
+// ---- speech segments ----------------------------------------------------------
+// One wave per clip. The scan is a serial state machine, so it runs in
+// wave-uniform code: each step loads 64 probabilities (one per lane), turns
+// them into two ballot masks (speech: p >= thr, silence: p < neg; a lane past
+// the clip's end sets neither) and walks the masks bit by bit with the state
+// in scalar registers. A segment is final once its successor is known (the
+// padding rule moves only e_k and s_{k+1}), so padding and the piece layout
+// are done on the fly with one pending segment; lane 0 stores the results.
+__global__ __launch_bounds__(64) void vad_segments_kernel(
+    const float* __restrict__ probs, const int* __restrict__ n_samples,
+    const int* __restrict__ chunk_off, int n_clips, const VadSegParams* __restrict__ prm,
+    int prm_stride, long long* __restrict__ tables) {
+  const int b = blockIdx.x;
+  if (b >= n_clips) return;
+  const int lane = threadIdx.x;
+  const int off = chunk_off[b];
+  const int nch = chunk_off[b + 1] - off;
+  const long long N = n_samples[b];
+  const VadSegParams P = prm[(size_t)b * prm_stride];
+  const int cap = nch + 1;
+  long long* __restrict__ T = tables + vad_table_off(off, b);
+  long long* __restrict__ seg = T + 2;
+  long long* __restrict__ pc = T + 2 + 2LL * cap;
+
+  int m = 0;            // final segments written
+  bool have = false;    // one emitted segment whose end is not final yet
+  long long ps = 0, pe = 0;
+  long long c = 0;      // compacted position of the pending segment's piece
+  auto put = [&](long long s, long long e, long long len) {
+    if (lane == 0 && m < cap) {
+      seg[2 * m] = s;
+      seg[2 * m + 1] = e;
+      pc[3 * m] = s;
+      pc[3 * m + 1] = len;
+      pc[3 * m + 2] = c;
+    }
+    ++m;
+  };
+  auto emit = [&](long long s, long long e) {
+    if (have) {
+      const long long gap = s - pe;
+      if (gap < 2 * P.pad) {
+        pe += gap >> 1;
+        s = max(0LL, s - (gap >> 1));
+      } else {
+        pe = min(N, pe + P.pad);
+        s = max(0LL, s - P.pad);
+      }
+      const long long end = min(pe + P.ov, s);
+      put(ps, pe, end - ps);
+      c += (end - ps) + (end == s ? 0 : VAD_GAP);
+    } else {
+      s = max(0LL, s - P.pad);
+    }
+    have = true;
+    ps = s;
+    pe = e;
+  };
+
+  bool trig = false;
+  long long start = 0, temp_end = 0, prev_end = 0, next_start = 0;
+  const float* __restrict__ p = probs + off;
+  float nxt = lane < nch ? p[lane] : 0.0f;
+  for (int base = 0; base < nch; base += 64) {
+    const float v = nxt;
+    const bool valid = base + lane < nch;
+    if (base + 64 + lane < nch) nxt = p[base + 64 + lane];
+    const unsigned long long ms = __ballot(valid && v >= P.thr);
+    const unsigned long long ml = __ballot(valid && v < P.neg);
+    const int cnt = min(64, nch - base);
+    for (int j = 0; j < cnt; ++j) {
+      const bool sp = (ms >> j) & 1, sl = (ml >> j) & 1;
+      const long long cur = (long long)VAD_CHUNK * (base + j);
+      if (sp && temp_end != 0) {
+        temp_end = 0;
+        if (next_start < prev_end) next_start = cur;
+      }
+      if (sp && !trig) {
+        trig = true;
+        start = cur;
+        continue;
+      }
+      if (trig && cur - start > P.max_speech) {
+        if (prev_end > 0) {
+          emit(start, prev_end);
+          if (next_start < prev_end)
+            trig = false;
+          else
+            start = next_start;
+          prev_end = next_start = temp_end = 0;
+        } else {
+          emit(start, cur);
+          prev_end = next_start = temp_end = 0;
+          trig = false;
+          continue;
+        }
+      }
+      if (sl && trig) {
+        if (temp_end == 0) temp_end = cur;
+        if (cur - temp_end > VAD_SIL_AT_MAX) prev_end = temp_end;
+        if (cur - temp_end < P.min_sil) continue;
+        if (temp_end - start > P.min_speech) emit(start, temp_end);
+        prev_end = next_start = temp_end = 0;
+        trig = false;
+      }
+    }
+  }
+  if (trig && N - start > P.min_speech) emit(start, N);
+  if (have) {
+    pe = min(N, pe + P.pad);
+    put(ps, pe, pe - ps);
+    c += pe - ps;
+  }
+  if (lane == 0) {
+    T[0] = min(m, cap);
+    T[1] = c;
+  }
+}
+
+// ---- compaction ---------------------------------------------------------------
+// grid.x = n_clips * tiles (tiles = ceil(max_len / VAD_CP_TILE)); workgroup
+// (clip b, tile x) writes compacted samples [x * VAD_CP_TILE, ...) of clip b
+// and leaves at once when the clip is shorter. It finds the piece of its first
+// sample by binary search over dst and moves on piece by piece from there;
+// a position past its piece's len lies in the gap and gets a zero. Loads and
+// stores are one dword per lane, consecutive lanes consecutive samples: the
+// sources have any 4-byte alignment.
+constexpr int VAD_CP_THREADS = 256;
+
+__global__ __launch_bounds__(VAD_CP_THREADS) void vad_compact_kernel(
+    const float* const* __restrict__ pcm, const int* __restrict__ n_samples,
+    const int* __restrict__ chunk_off, int n_clips, int tiles,
+    const long long* __restrict__ tables, const long long* __restrict__ out_off,
+    float* __restrict__ out) {
+  const int b = blockIdx.x / tiles;
+  if (b >= n_clips) return;
+  const int off = chunk_off[b];
+  const int cap = chunk_off[b + 1] - off + 1;
+  const long long* __restrict__ T = tables + vad_table_off(off, b);
+  const int m = (int)T[0];
+  const long long clen = T[1];
+  const long long o0 = (long long)(blockIdx.x % tiles) * VAD_CP_TILE;
+  if (m <= 0 || o0 >= clen) return;
+  const long long o1 = min(clen, o0 + VAD_CP_TILE);
+  const long long* __restrict__ pc = T + 2 + 2LL * cap;
+  int lo = 0, hi = m - 1;  // the last piece with dst <= o0 (dst_0 = 0)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (pc[3 * mid + 2] <= o0)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  int k = lo;
+  const float* __restrict__ src = pcm[b];
+  const long long N = n_samples[b];
+  float* __restrict__ dst = out + out_off[b];
+  long long ks = pc[3 * k], kl = pc[3 * k + 1], kd = pc[3 * k + 2];
+  long long nd = k + 1 < m ? pc[3 * (k + 1) + 2] : clen;
+  for (long long x = o0 + threadIdx.x; x < o1; x += VAD_CP_THREADS) {
+    while (x >= nd && k + 1 < m) {
+      ++k;
+      ks = pc[3 * k];
+      kl = pc[3 * k + 1];
+      kd = pc[3 * k + 2];
+      nd = k + 1 < m ? pc[3 * (k + 1) + 2] : clen;
+    }
+    const long long r = x - kd;
+    dst[x] = (r < kl && ks + r < N) ? src[ks + r] : 0.0f;
+  }
+}
+
 void vad_frontend_launch(const VadWeights& w, const float* const* pcm, const int* n_samples,
                          const int* chunk_off, int n_clips, int max_chunks, float* pre,
                          hipStream_t st) {
@@ -258,6 +435,23 @@ void vad_lstm_launch(const VadWeights& w, const float* pre, const int* chunk_off
   if (n_clips <= 0) return;
   vad_lstm_kernel<<<n_clips, VAD_GATES, 0, st>>>(w.whh_t, w.w_f, w.b_f, pre, chunk_off, n_clips,
                                                  probs);
+}
+
+void vad_segments_launch(const float* probs, const int* n_samples, const int* chunk_off,
+                         int n_clips, const VadSegParams* prm, int prm_stride, long long* tables,
+                         hipStream_t st) {
+  if (n_clips <= 0) return;
+  vad_segments_kernel<<<n_clips, 64, 0, st>>>(probs, n_samples, chunk_off, n_clips, prm,
+                                              prm_stride, tables);
+}
+
+void vad_compact_launch(const float* const* pcm, const int* n_samples, const int* chunk_off,
+                        int n_clips, const long long* tables, const long long* out_off,
+                        long long max_len, float* out, hipStream_t st) {
+  if (n_clips <= 0 || max_len <= 0) return;
+  const long long tiles = (max_len + VAD_CP_TILE - 1) / VAD_CP_TILE;
+  vad_compact_kernel<<<(unsigned)(tiles * n_clips), VAD_CP_THREADS, 0, st>>>(
+      pcm, n_samples, chunk_off, n_clips, (int)tiles, tables, out_off, out);
 }
 
 }  // namespace mwx

@@ -492,4 +492,34 @@ void vad_frontend_launch(const VadWeights& w, const float* const* pcm, const int
 void vad_lstm_launch(const VadWeights& w, const float* pre, const int* chunk_off, int n_clips,
                      float* probs, hipStream_t st);
 
+// Speech segments and silence trimming (k_vad.hip; the rule is DESIGN.md D7 /
+// INTEGRATION.md "VAD speech segments"). Every position is a sample index held
+// in 64 bits.
+constexpr int VAD_SIL_AT_MAX = 1568;  // silence that marks a possible split point
+constexpr int VAD_GAP = 1600;         // zeros between two non-adjacent pieces
+constexpr int VAD_CP_TILE = 4096;     // compacted samples per compaction workgroup
+struct VadSegParams {                 // mwx_vad_params, derived
+  float thr, neg;
+  long long min_speech, min_sil, pad, max_speech, ov;
+};
+// Clip b's table starts vad_table_off(chunk_off[b], b) int64 entries into the
+// table buffer and holds 2 + 5 cap of them, cap = its chunk count + 1 (every
+// segment starts at a chunk of its own, so there are at most that many):
+//   [0] segment count m   [1] compacted length
+//   [2 ..) m segments (start, end)   [2 + 2 cap ..) m pieces (src, len, dst)
+__host__ __device__ inline long long vad_table_off(long long chunk_off_b, long long b) {
+  return 5 * chunk_off_b + 7 * b;
+}
+// One wave per clip: scan + padding + piece layout of probs (rows chunk_off[b]
+// .. of a [total chunks] buffer). prm holds one entry (prm_stride 0) or one per
+// clip (prm_stride 1).
+void vad_segments_launch(const float* probs, const int* n_samples, const int* chunk_off,
+                         int n_clips, const VadSegParams* prm, int prm_stride, long long* tables,
+                         hipStream_t st);
+// Gathers every clip's pieces (and the gap zeros) into out + out_off[b]
+// (16-byte aligned starts); max_len = the longest compacted length.
+void vad_compact_launch(const float* const* pcm, const int* n_samples, const int* chunk_off,
+                        int n_clips, const long long* tables, const long long* out_off,
+                        long long max_len, float* out, hipStream_t st);
+
 }  // namespace mwx

@@ -1,7 +1,8 @@
 // Voice-activity detection: the model file (reader and seeded writer), the
-// VAD context and the mwx_vad_* entry points of include/mwx.h. The kernels are
-// in k_vad.hip; the network and the file layout are written down in
-// INTEGRATION.md ("VAD model").
+// VAD context and the mwx_vad_* entry points of include/mwx.h, speech segments
+// and silence trimming (mwx_vad_segments_*, mwx_vad_trim_batch) included. The
+// kernels are in k_vad.hip; the network, the file layout and the segment rule
+// are written down in INTEGRATION.md ("VAD model", "VAD speech segments").
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,8 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "mwx_test.h"
+#include "vad_trim.h"
 
 #define HIPC(x)                                                                        \
   do {                                                                                 \
@@ -243,13 +246,15 @@ bool vad_is_device_ptr(const void* p) {
 struct mwx_vad_context {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  bool timed = false;
+  // front end | recurrence | segments, then around the compaction
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool timed = false, timed_trim = false;
   float* d_weights = nullptr;
   mwx::VadWeights w{};
-  mwx::VBuf d_pcm, d_pre, d_probs, d_meta;
-  mwx::PinBuf h_meta, h_probs;
+  mwx::VBuf d_pcm, d_pre, d_probs, d_meta, d_tab, d_ooff;
+  mwx::PinBuf h_meta, h_probs, h_tab, h_ooff;
   std::vector<float> probs;  // mwx_vad_probs
+  int probs_n_samples = 0;   // the clip length they belong to
 };
 
 namespace mwx {
@@ -263,8 +268,12 @@ void vad_destroy(mwx_vad_context* v) {
   v->d_pre.release();
   v->d_probs.release();
   v->d_meta.release();
+  v->d_tab.release();
+  v->d_ooff.release();
   v->h_meta.release();
   v->h_probs.release();
+  v->h_tab.release();
+  v->h_ooff.release();
   {
     std::lock_guard<std::recursive_mutex> lock(capture_mutex());
     if (v->d_weights) (void)hipFree(v->d_weights);
@@ -335,69 +344,255 @@ void vad_upload(mwx_vad_context* v, std::map<std::string, std::vector<float>>& t
   v->w.b_f = t["_model.decoder.decoder.2.bias"][0];
 }
 
-int vad_run(mwx_vad_context* v, const float* const* samples, const int* n_samples, int n_clips,
-            float* probs_out, const int* probs_offset) {
+// mwx_vad_params -> the integers of the rule; false (logged)
+// for values outside it.
+bool vad_derive_params(const mwx_vad_params& p, VadSegParams& d) {
+  auto bad = [](const char* what) {
+    MWX_LOG_ERROR("mwx_vad: invalid parameters (%s)\n", what);
+    return false;
+  };
+  if (std::isnan(p.threshold) || std::isnan(p.max_speech_duration_s) ||
+      std::isnan(p.samples_overlap))
+    return bad("NaN");
+  if (!(p.threshold > 0.0f && p.threshold < 1.0f)) return bad("threshold outside (0, 1)");
+  if (p.min_speech_duration_ms < 0 || p.min_silence_duration_ms < 0 || p.speech_pad_ms < 0)
+    return bad("negative duration");
+  if (!(p.max_speech_duration_s > 0.0f)) return bad("max_speech_duration_s <= 0");
+  if (p.samples_overlap < 0.0f) return bad("samples_overlap < 0");
+  if (p.samples_overlap > 100000.0f) return bad("samples_overlap too large");
+  d.thr = p.threshold;
+  d.neg = std::max(p.threshold - 0.15f, 0.01f);
+  d.min_speech = 16LL * p.min_speech_duration_ms;
+  d.min_sil = 16LL * p.min_silence_duration_ms;
+  d.pad = 16LL * p.speech_pad_ms;
+  const double ms = (double)p.max_speech_duration_s * 16000.0 - 512.0 - 2.0 * (double)d.pad;
+  d.max_speech = (long long)std::min(ms, 4611686018427387904.0 /* 2^62 */);
+  d.ov = (int)(p.samples_overlap * 16000.0f);
+  return true;
+}
+
+// One call's inputs as the kernels see them.
+struct VadPass {
+  std::vector<int> off;  // chunk prefix sums
+  int total = 0, max_chunks = 0;
+  const float* const* d_ptrs = nullptr;
+  const int* d_ns = nullptr;
+  const int* d_off = nullptr;
+  const VadSegParams* d_prm = nullptr;
+};
+
+// Chunk prefix sums of the clips; < 0 on bad arguments.
+int vad_chunk_offsets(const int* n_samples, int n_clips, VadPass& ps) {
+  ps.off.assign((size_t)n_clips + 1, 0);
+  ps.max_chunks = 0;
+  for (int b = 0; b < n_clips; ++b) {
+    if (n_samples[b] < 0) return -2;
+    const int nc = mwx_vad_n_chunks(n_samples[b]);
+    if ((long)ps.off[b] + nc > 0x7fffffffL) return -3;
+    ps.off[b + 1] = ps.off[b] + nc;
+    ps.max_chunks = std::max(ps.max_chunks, nc);
+  }
+  ps.total = ps.off[n_clips];
+  return 0;
+}
+
+// meta: [clip pointers][n_samples][chunk_off][segment parameters], one upload
+void vad_upload_meta(mwx_vad_context* v, const std::vector<const float*>& ptrs,
+                     const int* n_samples, int n_clips, const VadSegParams* prm, int n_prm,
+                     VadPass& ps) {
+  hipStream_t st = v->stream;
+  const size_t m_ptr = 0, m_ns = m_ptr + (size_t)n_clips * 8, m_off = m_ns + (size_t)n_clips * 4;
+  const size_t m_prm = (m_off + ((size_t)n_clips + 1) * 4 + 7) / 8 * 8;
+  const size_t m_bytes = m_prm + (size_t)n_prm * sizeof(VadSegParams);
+  char* hm = (char*)v->h_meta.get(m_bytes);
+  char* dm = (char*)v->d_meta.get(m_bytes, st);
+  memcpy(hm + m_ptr, ptrs.data(), (size_t)n_clips * 8);
+  memcpy(hm + m_ns, n_samples, (size_t)n_clips * 4);
+  memcpy(hm + m_off, ps.off.data(), ((size_t)n_clips + 1) * 4);
+  if (n_prm > 0) memcpy(hm + m_prm, prm, (size_t)n_prm * sizeof(VadSegParams));
+  HIPC(hipMemcpyAsync(dm, hm, m_bytes, hipMemcpyHostToDevice, st));
+  ps.d_ptrs = (const float* const*)(dm + m_ptr);
+  ps.d_ns = (const int*)(dm + m_ns);
+  ps.d_off = (const int*)(dm + m_off);
+  ps.d_prm = n_prm > 0 ? (const VadSegParams*)(dm + m_prm) : nullptr;
+}
+
+// Stages the host clips back to back in d_pcm, uploads the meta block and runs
+// the two network kernels; the probabilities are in d_probs when the stream
+// gets there. ps.total == 0: nothing was launched.
+int vad_forward(mwx_vad_context* v, const float* const* samples, const int* n_samples, int n_clips,
+                const VadSegParams* prm, int n_prm, VadPass& ps) {
   HIPC(hipSetDevice(v->device));
-  v->timed = false;
-  // chunk prefix sums; host clips are staged back to back in d_pcm
-  std::vector<int> off((size_t)n_clips + 1, 0);
+  v->timed = v->timed_trim = false;
   std::vector<size_t> stage((size_t)n_clips, 0);
   std::vector<char> on_device((size_t)n_clips, 0);
   size_t stage_floats = 0;
-  int max_chunks = 0;
-  for (int b = 0; b < n_clips; ++b) {
-    if (n_samples[b] < 0 || (n_samples[b] > 0 && !samples[b])) return -2;
-    const int nc = mwx_vad_n_chunks(n_samples[b]);
-    if ((long)off[b] + nc > 0x7fffffffL) return -3;
-    off[b + 1] = off[b] + nc;
-    max_chunks = std::max(max_chunks, nc);
+  for (int b = 0; b < n_clips; ++b)
+    if (n_samples[b] > 0 && !samples[b]) return -2;
+  const int rc = vad_chunk_offsets(n_samples, n_clips, ps);
+  if (rc != 0) return rc;
+  for (int b = 0; b < n_clips; ++b)
     if (n_samples[b] > 0 && !(on_device[b] = vad_is_device_ptr(samples[b]))) {
       stage[b] = stage_floats;
       stage_floats += ((size_t)n_samples[b] + 3) / 4 * 4;
     }
-  }
-  const int total = off[n_clips];
-  if (total == 0) return 0;
-  const long tiles = (max_chunks + VAD_TILE - 1) / VAD_TILE;  // front-end grid = clips x tiles
+  if (ps.total == 0) return 0;
+  const long tiles = (ps.max_chunks + VAD_TILE - 1) / VAD_TILE;  // front-end grid = clips x tiles
   if (tiles * n_clips > 0x7fffffffL) return -3;
   hipStream_t st = v->stream;
   float* d_pcm = stage_floats ? (float*)v->d_pcm.get(stage_floats * 4, st) : nullptr;
-  // meta: [clip pointers][n_samples][chunk_off]
-  const size_t m_ptr = 0, m_ns = m_ptr + (size_t)n_clips * 8, m_off = m_ns + (size_t)n_clips * 4;
-  const size_t m_bytes = m_off + ((size_t)n_clips + 1) * 4;
-  char* hm = (char*)v->h_meta.get(m_bytes);
-  char* dm = (char*)v->d_meta.get(m_bytes, st);
+  std::vector<const float*> ptrs((size_t)n_clips);
   for (int b = 0; b < n_clips; ++b) {
-    const float* p = samples[b];
+    ptrs[b] = samples[b];
     if (n_samples[b] > 0 && !on_device[b]) {
       HIPC(hipMemcpyAsync(d_pcm + stage[b], samples[b], (size_t)n_samples[b] * 4,
                           hipMemcpyHostToDevice, st));
-      p = d_pcm + stage[b];
+      ptrs[b] = d_pcm + stage[b];
     }
-    memcpy(hm + m_ptr + (size_t)b * 8, &p, 8);
   }
-  memcpy(hm + m_ns, n_samples, (size_t)n_clips * 4);
-  memcpy(hm + m_off, off.data(), ((size_t)n_clips + 1) * 4);
-  HIPC(hipMemcpyAsync(dm, hm, m_bytes, hipMemcpyHostToDevice, st));
-  float* d_pre = (float*)v->d_pre.get((size_t)total * VAD_GATES * 4, st);
-  float* d_probs = (float*)v->d_probs.get((size_t)total * 4, st);
-  float* h_probs = (float*)v->h_probs.get((size_t)total * 4);
-  const float* const* d_ptrs = (const float* const*)(dm + m_ptr);
-  const int* d_ns = (const int*)(dm + m_ns);
-  const int* d_off = (const int*)(dm + m_off);
+  vad_upload_meta(v, ptrs, n_samples, n_clips, prm, n_prm, ps);
+  float* d_pre = (float*)v->d_pre.get((size_t)ps.total * VAD_GATES * 4, st);
+  float* d_probs = (float*)v->d_probs.get((size_t)ps.total * 4, st);
   HIPC(hipEventRecord(v->ev[0], st));
-  vad_frontend_launch(v->w, d_ptrs, d_ns, d_off, n_clips, max_chunks, d_pre, st);
+  vad_frontend_launch(v->w, ps.d_ptrs, ps.d_ns, ps.d_off, n_clips, ps.max_chunks, d_pre, st);
   HIPC(hipEventRecord(v->ev[1], st));
-  vad_lstm_launch(v->w, d_pre, d_off, n_clips, d_probs, st);
+  vad_lstm_launch(v->w, d_pre, ps.d_off, n_clips, d_probs, st);
   HIPC(hipEventRecord(v->ev[2], st));
   HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(h_probs, d_probs, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+  return 0;
+}
+
+int vad_run(mwx_vad_context* v, const float* const* samples, const int* n_samples, int n_clips,
+            float* probs_out, const int* probs_offset) {
+  VadPass ps;
+  const int rc = vad_forward(v, samples, n_samples, n_clips, nullptr, 0, ps);
+  if (rc != 0 || ps.total == 0) return rc;
+  hipStream_t st = v->stream;
+  float* h_probs = (float*)v->h_probs.get((size_t)ps.total * 4);
+  HIPC(hipMemcpyAsync(h_probs, v->d_probs.p, (size_t)ps.total * 4, hipMemcpyDeviceToHost, st));
   HIPC(hipStreamSynchronize(st));
   v->timed = true;
   for (int b = 0; b < n_clips; ++b)
-    if (off[b + 1] > off[b])
-      memcpy(probs_out + probs_offset[b], h_probs + off[b], (size_t)(off[b + 1] - off[b]) * 4);
+    if (ps.off[b + 1] > ps.off[b])
+      memcpy(probs_out + probs_offset[b], h_probs + ps.off[b],
+             (size_t)(ps.off[b + 1] - ps.off[b]) * 4);
   return 0;
+}
+
+// vad_segments_kernel over the probabilities in d_probs, then the one copy
+// back: the tables of every clip (kernels.h, vad_table_off) in pinned memory,
+// valid until the context's next call. Synchronizes.
+const int64_t* vad_segment_tables(mwx_vad_context* v, int n_clips, int prm_stride,
+                                  const VadPass& ps) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "table entries");
+  hipStream_t st = v->stream;
+  const size_t n_tab = (size_t)vad_table_off(ps.total, n_clips);
+  long long* d_tab = (long long*)v->d_tab.get(n_tab * 8, st);
+  int64_t* h_tab = (int64_t*)v->h_tab.get(n_tab * 8);
+  vad_segments_launch((const float*)v->d_probs.p, ps.d_ns, ps.d_off, n_clips, ps.d_prm,
+                      prm_stride, d_tab, st);
+  HIPC(hipEventRecord(v->ev[3], st));
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(h_tab, d_tab, n_tab * 8, hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  return h_tab;
+}
+
+// Clip b's table -> segments and pieces; false when the table is not one the
+// kernel can have written.
+bool vad_read_table(const int64_t* h_tab, const VadPass& ps, int b, std::vector<int64_t>& seg,
+                    std::vector<int64_t>& piece, int64_t& n_compact) {
+  const int64_t* T = h_tab + vad_table_off(ps.off[b], b);
+  const int64_t cap = ps.off[b + 1] - ps.off[b] + 1;
+  const int64_t m = T[0];
+  if (m < 0 || m > cap || T[1] < 0) return false;
+  seg.assign(T + 2, T + 2 + 2 * m);
+  piece.assign(T + 2 + 2 * cap, T + 2 + 2 * cap + 3 * m);
+  n_compact = T[1];
+  return true;
+}
+
+// The segment kernel over caller-supplied probabilities (clip b's at
+// probs + probs_offset[b]): mwx_vad_segments_from_probs and the test hook.
+// prm: one entry per clip.
+int vad_segments_of_probs(mwx_vad_context* v, const VadSegParams* prm, const float* probs,
+                          const int* probs_offset, const int* n_samples, int n_clips,
+                          std::vector<mwx_vad_trimmed::Clip>& out) {
+  HIPC(hipSetDevice(v->device));
+  v->timed = v->timed_trim = false;
+  VadPass ps;
+  const int rc = vad_chunk_offsets(n_samples, n_clips, ps);
+  if (rc != 0) return rc;
+  out.assign((size_t)n_clips, mwx_vad_trimmed::Clip());
+  hipStream_t st = v->stream;
+  float* h_probs = (float*)v->h_probs.get((size_t)std::max(ps.total, 1) * 4);
+  float* d_probs = (float*)v->d_probs.get((size_t)std::max(ps.total, 1) * 4, st);
+  for (int b = 0; b < n_clips; ++b)
+    if (ps.off[b + 1] > ps.off[b])
+      memcpy(h_probs + ps.off[b], probs + probs_offset[b],
+             (size_t)(ps.off[b + 1] - ps.off[b]) * 4);
+  if (ps.total > 0)
+    HIPC(hipMemcpyAsync(d_probs, h_probs, (size_t)ps.total * 4, hipMemcpyHostToDevice, st));
+  vad_upload_meta(v, std::vector<const float*>((size_t)n_clips, nullptr), n_samples, n_clips, prm,
+                  n_clips, ps);
+  const int64_t* h_tab = vad_segment_tables(v, n_clips, 1, ps);
+  for (int b = 0; b < n_clips; ++b)
+    if (!vad_read_table(h_tab, ps, b, out[b].seg, out[b].piece, out[b].n_compact)) return -5;
+  return 0;
+}
+
+// VAD, segments and compaction of all clips; fills t (whose d_pcm the caller
+// frees, also after an exception).
+int vad_trim_run(mwx_vad_context* v, const VadSegParams& prm, const float* const* samples,
+                 const int* n_samples, int n_clips, mwx_vad_trimmed& t) {
+  t.device = v->device;
+  t.clips.assign((size_t)n_clips, mwx_vad_trimmed::Clip());
+  VadPass ps;
+  const int rc = vad_forward(v, samples, n_samples, n_clips, &prm, 1, ps);
+  if (rc != 0 || ps.total == 0) return rc;
+  hipStream_t st = v->stream;
+  const int64_t* h_tab = vad_segment_tables(v, n_clips, 0, ps);
+  size_t total = 0;
+  int64_t max_len = 0;
+  int64_t* h_ooff = (int64_t*)v->h_ooff.get((size_t)n_clips * 8);
+  for (int b = 0; b < n_clips; ++b) {
+    mwx_vad_trimmed::Clip& c = t.clips[b];
+    if (!vad_read_table(h_tab, ps, b, c.seg, c.piece, c.n_compact)) return -5;
+    c.off = total;
+    h_ooff[b] = (int64_t)total;
+    total += ((size_t)c.n_compact + 3) / 4 * 4;  // 16-byte aligned clip starts
+    max_len = std::max(max_len, c.n_compact);
+  }
+  v->timed = true;
+  if (total == 0) return 0;
+  const int64_t tiles = (max_len + VAD_CP_TILE - 1) / VAD_CP_TILE;  // compaction grid = clips x tiles
+  if (tiles * n_clips > 0x7fffffffL) return -3;
+  {
+    std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+    HIPC(hipMalloc((void**)&t.d_pcm, total * 4));
+  }
+  long long* d_ooff = (long long*)v->d_ooff.get((size_t)n_clips * 8, st);
+  HIPC(hipMemcpyAsync(d_ooff, h_ooff, (size_t)n_clips * 8, hipMemcpyHostToDevice, st));
+  HIPC(hipEventRecord(v->ev[4], st));
+  vad_compact_launch(ps.d_ptrs, ps.d_ns, ps.d_off, n_clips, (const long long*)v->d_tab.p, d_ooff,
+                     max_len, t.d_pcm, st);
+  HIPC(hipEventRecord(v->ev[5], st));
+  HIPC(hipGetLastError());
+  // the object is complete, and independent of this context's buffers, when
+  // the call returns
+  HIPC(hipStreamSynchronize(st));
+  v->timed_trim = true;
+  return 0;
+}
+
+void vad_trimmed_destroy(mwx_vad_trimmed* t) {
+  if (!t) return;
+  if (t->d_pcm) {
+    (void)hipSetDevice(t->device);
+    std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+    (void)hipFree(t->d_pcm);
+  }
+  delete t;
 }
 
 }  // namespace
@@ -464,6 +659,7 @@ bool mwx_vad_detect_speech(struct mwx_vad_context* vctx, const float* samples, i
                                              out.empty() ? &dummy : out.data(), &zero);
   if (rc != 0) return false;
   vctx->probs = std::move(out);
+  vctx->probs_n_samples = n_samples;
   return true;
 }
 
@@ -482,6 +678,171 @@ int mwx_vad_last_kernel_ms(struct mwx_vad_context* vctx, float* frontend_ms, flo
   if (frontend_ms) *frontend_ms = a;
   if (lstm_ms) *lstm_ms = b;
   return 0;
+}
+
+// ---- speech segments and trimming ---------------------------------------------
+struct mwx_vad_params mwx_vad_default_params(void) {
+  mwx_vad_params p;
+  p.threshold = 0.5f;
+  p.min_speech_duration_ms = 250;
+  p.min_silence_duration_ms = 100;
+  p.max_speech_duration_s = 3.402823466e+38f;  // FLT_MAX
+  p.speech_pad_ms = 30;
+  p.samples_overlap = 0.1f;
+  return p;
+}
+
+struct mwx_vad_segments* mwx_vad_segments_from_probs(struct mwx_vad_context* vctx,
+                                                     struct mwx_vad_params params) {
+  if (!vctx) return nullptr;
+  mwx::VadSegParams prm;
+  if (!mwx::vad_derive_params(params, prm)) return nullptr;
+  const int n = vctx->probs_n_samples, zero = 0;
+  if (mwx_vad_n_chunks(n) != (int)vctx->probs.size()) return nullptr;
+  try {
+    const std::vector<float>& probs = vctx->probs;
+    const float dummy = 0.0f;
+    std::vector<mwx_vad_trimmed::Clip> out;
+    if (mwx::vad_segments_of_probs(vctx, &prm, probs.empty() ? &dummy : probs.data(), &zero, &n,
+                                   1, out) != 0)
+      return nullptr;
+    mwx_vad_segments* s = new mwx_vad_segments();
+    s->seg = std::move(out[0].seg);
+    return s;
+  } catch (const std::exception&) {
+    return nullptr;
+  }
+}
+
+struct mwx_vad_segments* mwx_vad_segments_from_samples(struct mwx_vad_context* vctx,
+                                                       struct mwx_vad_params params,
+                                                       const float* samples, int n_samples) {
+  mwx::VadSegParams prm;
+  if (!vctx || !mwx::vad_derive_params(params, prm)) return nullptr;
+  if (!mwx_vad_detect_speech(vctx, samples, n_samples)) return nullptr;
+  return mwx_vad_segments_from_probs(vctx, params);
+}
+
+int mwx_vad_segments_n_segments(struct mwx_vad_segments* s) {
+  return s ? (int)(s->seg.size() / 2) : 0;
+}
+float mwx_vad_segments_get_segment_t0(struct mwx_vad_segments* s, int i) {
+  return (float)s->seg.at(2 * (size_t)i) / 160.0f;
+}
+float mwx_vad_segments_get_segment_t1(struct mwx_vad_segments* s, int i) {
+  return (float)s->seg.at(2 * (size_t)i + 1) / 160.0f;
+}
+void mwx_vad_free_segments(struct mwx_vad_segments* s) { delete s; }
+
+struct mwx_vad_trimmed* mwx_vad_trim_batch(struct mwx_vad_context* vctx,
+                                           struct mwx_vad_params params,
+                                           const float* const* samples, const int* n_samples,
+                                           int n_clips) {
+  if (!vctx || n_clips < 0 || (n_clips > 0 && (!samples || !n_samples))) return nullptr;
+  mwx::VadSegParams prm;
+  if (!mwx::vad_derive_params(params, prm)) return nullptr;
+  mwx_vad_trimmed* t = new mwx_vad_trimmed();
+  t->device = vctx->device;
+  if (n_clips == 0) return t;
+  int rc = -4;
+  try {
+    rc = mwx::vad_trim_run(vctx, prm, samples, n_samples, n_clips, *t);
+  } catch (const std::exception&) {
+  }
+  if (rc != 0) {
+    MWX_LOG_ERROR("mwx_vad_trim_batch failed (%d)\n", rc);
+    mwx::vad_trimmed_destroy(t);
+    return nullptr;
+  }
+  return t;
+}
+
+int mwx_vad_trimmed_n_clips(const struct mwx_vad_trimmed* t) { return t ? (int)t->clips.size() : 0; }
+
+#define MWX_TRIM_CLIP(t, clip, fail) \
+  if (!(t) || (clip) < 0 || (size_t)(clip) >= (t)->clips.size()) return fail
+
+int mwx_vad_trimmed_n_segments(const struct mwx_vad_trimmed* t, int clip) {
+  MWX_TRIM_CLIP(t, clip, -1);
+  return (int)(t->clips[clip].seg.size() / 2);
+}
+int mwx_vad_trimmed_segment(const struct mwx_vad_trimmed* t, int clip, int i, int64_t* s0,
+                            int64_t* s1) {
+  MWX_TRIM_CLIP(t, clip, -1);
+  const std::vector<int64_t>& seg = t->clips[clip].seg;
+  if (i < 0 || 2 * (size_t)i + 1 >= seg.size()) return -1;
+  if (s0) *s0 = seg[2 * (size_t)i];
+  if (s1) *s1 = seg[2 * (size_t)i + 1];
+  return 0;
+}
+int64_t mwx_vad_trimmed_n_samples(const struct mwx_vad_trimmed* t, int clip) {
+  MWX_TRIM_CLIP(t, clip, -1);
+  return t->clips[clip].n_compact;
+}
+const float* mwx_vad_trimmed_pcm(const struct mwx_vad_trimmed* t, int clip) {
+  MWX_TRIM_CLIP(t, clip, nullptr);
+  return t->clips[clip].n_compact > 0 ? t->d_pcm + t->clips[clip].off : nullptr;
+}
+int64_t mwx_vad_trimmed_map_time(const struct mwx_vad_trimmed* t, int clip, int64_t t_cs,
+                                 bool is_end) {
+  MWX_TRIM_CLIP(t, clip, t_cs);
+  return mwx::vad_map_time(t->clips[clip], t_cs, is_end);
+}
+void mwx_vad_trimmed_free(struct mwx_vad_trimmed* t) { mwx::vad_trimmed_destroy(t); }
+
+int mwx_vad_last_trim_kernel_ms(struct mwx_vad_context* vctx, float* segments_ms,
+                                float* compact_ms) {
+  if (!vctx || !vctx->timed_trim) return -1;
+  float a = 0.0f, b = 0.0f;
+  if (hipEventElapsedTime(&a, vctx->ev[2], vctx->ev[3]) != hipSuccess ||
+      hipEventElapsedTime(&b, vctx->ev[4], vctx->ev[5]) != hipSuccess)
+    return -1;
+  if (segments_ms) *segments_ms = a;
+  if (compact_ms) *compact_ms = b;
+  return 0;
+}
+
+int mwx_test_vad_segments(struct mwx_vad_context* vctx, const struct mwx_vad_params* params,
+                          const float* probs, const int* probs_offset, const int* n_samples,
+                          int n_clips, int* n_segments, int64_t* compact_len, int64_t* segments,
+                          int64_t* pieces, const int* out_offset) {
+  if (!vctx || n_clips <= 0 || !params || !probs || !probs_offset || !n_samples || !n_segments ||
+      !compact_len || !segments || !pieces || !out_offset)
+    return -1;
+  std::vector<mwx::VadSegParams> prm((size_t)n_clips);
+  for (int b = 0; b < n_clips; ++b)
+    if (!mwx::vad_derive_params(params[b], prm[b])) return -2;
+  try {
+    std::vector<mwx_vad_trimmed::Clip> out;
+    const int rc = mwx::vad_segments_of_probs(vctx, prm.data(), probs, probs_offset, n_samples,
+                                              n_clips, out);
+    if (rc != 0) return rc;
+    for (int b = 0; b < n_clips; ++b) {
+      const mwx_vad_trimmed::Clip& c = out[b];
+      n_segments[b] = (int)(c.seg.size() / 2);
+      compact_len[b] = c.n_compact;
+      if (c.seg.size() / 2 > (size_t)mwx_vad_n_chunks(n_samples[b])) return -5;
+      std::copy(c.seg.begin(), c.seg.end(), segments + 2 * (size_t)out_offset[b]);
+      std::copy(c.piece.begin(), c.piece.end(), pieces + 3 * (size_t)out_offset[b]);
+    }
+    return 0;
+  } catch (const std::exception&) {
+    return -4;
+  }
+}
+
+int64_t mwx_test_vad_trimmed_pcm(const struct mwx_vad_trimmed* t, int clip, float* out,
+                                 int64_t cap) {
+  MWX_TRIM_CLIP(t, clip, -1);
+  const mwx_vad_trimmed::Clip& c = t->clips[clip];
+  if (c.n_compact > cap || (c.n_compact > 0 && !out)) return -2;
+  if (c.n_compact == 0) return 0;
+  if (hipSetDevice(t->device) != hipSuccess) return -4;
+  std::lock_guard<std::recursive_mutex> lock(mwx::capture_mutex());  // (legacy-stream copy)
+  if (hipMemcpy(out, t->d_pcm + c.off, (size_t)c.n_compact * 4, hipMemcpyDeviceToHost) !=
+      hipSuccess)
+    return -4;
+  return c.n_compact;
 }
 
 // ---- synthetic writer -------------------------------------------------------

@@ -20,10 +20,34 @@
 #pragma weak mwx_vad_probs
 #pragma weak mwx_vad_n_chunks
 #pragma weak mwx_vad_detect_speech_batch
+// ... and so are the trimming calls: without them vad_trim falls back to the gate
+#pragma weak mwx_vad_default_params
+#pragma weak mwx_vad_trim_batch
+#pragma weak mwx_vad_trimmed_n_segments
+#pragma weak mwx_vad_trimmed_free
+#pragma weak mwx_full_batch_trimmed
 
 namespace mwx_host {
 
+// The trimmed audio of one trim pass, and the object array of one
+// mwx_full_batch_trimmed call. Plain structs rather than standard containers
+// of the C type: the library's type then appears in no symbol of the host.
+struct TrimmedAudio {
+  mwx_vad_trimmed* t = nullptr;
+  ~TrimmedAudio() {
+    if (t) mwx_vad_trimmed_free(t);
+  }
+};
+
 namespace {
+
+struct TrimList {
+  const mwx_vad_trimmed** p;
+  explicit TrimList(size_t n) : p(new const mwx_vad_trimmed*[n]) {}
+  ~TrimList() { delete[] p; }
+  TrimList(const TrimList&) = delete;
+  TrimList& operator=(const TrimList&) = delete;
+};
 
 bool abort_trampoline(void* user_data) {
   auto* fn = static_cast<std::function<bool()>*>(user_data);
@@ -119,6 +143,9 @@ SttEngine::SttEngine(const Settings& settings) : settings_(settings) {
     }
     if (!vad_ctx_)
       std::fprintf(stderr, "SttEngine: VAD model %s not loaded, VAD disabled\n", vad_path.c_str());
+    trim_active_ = settings_.vad_trim && vad_ctx_ && mwx_vad_default_params &&
+                   mwx_vad_trim_batch && mwx_vad_trimmed_n_segments && mwx_vad_trimmed_free &&
+                   mwx_full_batch_trimmed;
   }
   const int pool = std::max(1, settings_.parallel_requests);
   if (settings_.max_batch > 1) {
@@ -168,13 +195,15 @@ std::string SttEngine::options_key(const RequestOptions& o) const {
   return std::string(buf) + lang + "|" + o.prompt;
 }
 
-std::vector<TranscriptionResult> SttEngine::transcribe_batched(const std::vector<float>& pcmf32,
-                                                               const RequestOptions& options,
-                                                               PerformanceMetrics* out_metrics) {
+std::vector<TranscriptionResult> SttEngine::transcribe_batched(
+    const std::vector<float>& pcmf32, const RequestOptions& options,
+    PerformanceMetrics* out_metrics, std::shared_ptr<TrimmedAudio> trimmed) {
   auto req = std::make_shared<Pending>();
   req->pcm = &pcmf32;
   req->options = options;
-  req->key = options_key(options);
+  // trimmed and untrimmed requests (a failed trim pass) never share a batch
+  req->key = options_key(options) + (trimmed ? "|trimmed" : "");
+  req->trimmed = std::move(trimmed);
   req->t_enq = std::chrono::steady_clock::now();
   std::unique_lock<std::mutex> lock(q_mutex_);
   queue_.push_back(req);
@@ -257,7 +286,16 @@ void SttEngine::batcher_loop(std::vector<mwx_state*> states) {
       ptrs.push_back(r->pcm->data());
       lens.push_back((int)r->pcm->size());
     }
-    const int ret = mwx_full_batch(ctx_, states.data(), p, ptrs.data(), lens.data(), (int)batch.size());
+    int ret;
+    if (batch[0]->trimmed) {
+      TrimList objs(batch.size());
+      for (size_t b = 0; b < batch.size(); ++b) objs.p[b] = batch[b]->trimmed->t;
+      const std::vector<int> first(batch.size(), 0);
+      ret = mwx_full_batch_trimmed(ctx_, states.data(), p, objs.p, first.data(),
+                                   (int)batch.size());
+    } else {
+      ret = mwx_full_batch(ctx_, states.data(), p, ptrs.data(), lens.data(), (int)batch.size());
+    }
     const auto t1 = std::chrono::steady_clock::now();
     batches_run_++;
     for (size_t b = 0; b < batch.size(); ++b) {
@@ -431,6 +469,17 @@ bool SttEngine::is_speech_detected(const float* pcm, size_t n_samples) {
   return false;
 }
 
+std::shared_ptr<TrimmedAudio> SttEngine::trim_clips(const float* const* pcm, const int* n_samples,
+                                                    int n_clips) {
+  if (!trim_active_) return nullptr;
+  mwx_vad_params vp = mwx_vad_default_params();
+  vp.threshold = settings_.vad_threshold;
+  auto out = std::make_shared<TrimmedAudio>();
+  std::lock_guard<std::mutex> lock(vad_mutex_);
+  out->t = mwx_vad_trim_batch(vad_ctx_, vp, pcm, n_samples, n_clips);
+  return out->t ? out : nullptr;
+}
+
 TranscriptionResult SttEngine::empty_result(size_t pcm_size) {
   TranscriptionResult r;
   r.text = "";
@@ -469,20 +518,39 @@ std::vector<TranscriptionResult> SttEngine::transcribe(const std::vector<float>&
     if (out_metrics) *out_metrics = {0.0, 0.0, 0};
     return {};
   }
-  // src/stt_engine.cpp:169-194: silence never reaches Whisper
-  if (settings_.enable_vad && !is_speech_detected(pcm.data(), pcm_size)) {
+  // src/stt_engine.cpp:169-194: silence never reaches Whisper. With vad_trim
+  // the trim pass is the gate (no segments = no speech); if it fails the clip
+  // goes on untrimmed, as a failed gate call leaves the gate open.
+  std::shared_ptr<TrimmedAudio> trimmed;
+  bool speech = true;
+  if (trim_active_) {
+    const float* p = pcm.data();
+    const int n = static_cast<int>(pcm_size);
+    trimmed = trim_clips(&p, &n, 1);
+    speech = !trimmed || mwx_vad_trimmed_n_segments(trimmed->t, 0) != 0;
+  } else if (settings_.enable_vad) {
+    speech = is_speech_detected(pcm.data(), pcm_size);
+  }
+  if (!speech) {
     if (out_metrics)
       *out_metrics = {0.0, ms_between(t_start, std::chrono::steady_clock::now()), 0};
     return {empty_result(pcm_size)};
   }
-  if (settings_.max_batch > 1) return transcribe_batched(pcm, options, out_metrics);
+  if (settings_.max_batch > 1) return transcribe_batched(pcm, options, out_metrics, trimmed);
   StateGuard guard(*this);
   mwx_state* state = guard.get();
   const auto t_acq = std::chrono::steady_clock::now();
   std::string lang;
   std::function<bool()> abort_fn = options.should_abort;
   const mwx_full_params p = make_params(options, lang, abort_fn);
-  const int ret = mwx_full_with_state(ctx_, state, p, pcm.data(), static_cast<int>(pcm_size));
+  int ret;
+  if (trimmed) {
+    const mwx_vad_trimmed* obj = trimmed->t;
+    const int first = 0;
+    ret = mwx_full_batch_trimmed(ctx_, &state, p, &obj, &first, 1);
+  } else {
+    ret = mwx_full_with_state(ctx_, state, p, pcm.data(), static_cast<int>(pcm_size));
+  }
   const auto t_end = std::chrono::steady_clock::now();
   if (out_metrics) *out_metrics = {ms_between(t_start, t_acq), ms_between(t_acq, t_end), 0};
   if (ret != 0) {
@@ -524,7 +592,36 @@ std::vector<std::vector<TranscriptionResult>> SttEngine::transcribe_batch(
   // VAD gate: one batched pass over the clips that pass the minimum duration;
   // a silent clip gets the empty result and is left out of the Whisper batch
   std::vector<size_t> run;  // indices of the clips that go to mwx_full_batch
-  if (vad_ctx_ && mwx_vad_detect_speech_batch && mwx_vad_n_chunks) {
+  // vad_trim: one trim pass over those clips instead; a clip without segments
+  // gets the empty result, the others are decoded from their trimmed audio.
+  // Shorter clips end with no result either way and are left out here.
+  std::shared_ptr<TrimmedAudio> trimmed;
+  std::vector<int> trim_index;  // run[i]'s clip in `trimmed`
+  if (trim_active_) {
+    std::vector<size_t> gated;
+    std::vector<const float*> vptrs;
+    std::vector<int> vlens;
+    for (size_t b = 0; b < clips.size(); ++b)
+      if (clips[b].size() >= min_samples) {
+        gated.push_back(b);
+        vptrs.push_back(clips[b].data());
+        vlens.push_back(static_cast<int>(clips[b].size()));
+      }
+    if (gated.empty()) return out;
+    trimmed = trim_clips(vptrs.data(), vlens.data(), static_cast<int>(gated.size()));
+    if (trimmed) {
+      for (size_t g = 0; g < gated.size(); ++g) {
+        if (mwx_vad_trimmed_n_segments(trimmed->t, static_cast<int>(g)) != 0) {
+          run.push_back(gated[g]);
+          trim_index.push_back(static_cast<int>(g));
+        } else {
+          out[gated[g]] = {empty_result(clips[gated[g]].size())};
+        }
+      }
+    } else {
+      for (size_t b = 0; b < clips.size(); ++b) run.push_back(b);  // failed: untrimmed
+    }
+  } else if (vad_ctx_ && mwx_vad_detect_speech_batch && mwx_vad_n_chunks) {
     std::vector<size_t> gated;
     std::vector<const float*> vptrs;
     std::vector<int> vlens, voff;
@@ -578,8 +675,16 @@ std::vector<std::vector<TranscriptionResult>> SttEngine::transcribe_batch(
   std::string lang;
   std::function<bool()> abort_fn = options.should_abort;
   const mwx_full_params p = make_params(options, lang, abort_fn);
-  const int ret = mwx_full_batch(ctx_, states.data(), p, ptrs.data(), lens.data(),
+  int ret;
+  if (trimmed) {
+    TrimList objs(run.size());
+    for (size_t i = 0; i < run.size(); ++i) objs.p[i] = trimmed->t;
+    ret = mwx_full_batch_trimmed(ctx_, states.data(), p, objs.p, trim_index.data(),
                                  static_cast<int>(run.size()));
+  } else {
+    ret = mwx_full_batch(ctx_, states.data(), p, ptrs.data(), lens.data(),
+                         static_cast<int>(run.size()));
+  }
   if (ret == 0) {
     for (size_t i = 0; i < run.size(); ++i) {
       const size_t b = run[i];

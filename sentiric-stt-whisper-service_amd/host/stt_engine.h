@@ -16,7 +16,9 @@
 // gate (is_speech_detected, :108-115, :169-194: on the GPU by mwx_vad_*; a clip
 // with no speech comes back as one empty result and never takes a state).
 // The gate's decision rule is this engine's own (deviation D6): any
-// chunk probability >= Settings::vad_threshold.
+// chunk probability >= Settings::vad_threshold. Settings::vad_trim (off by
+// default) replaces the gate by silence trimming: mwx_vad_trim_batch +
+// mwx_full_batch_trimmed (deviation D7).
 #pragma once
 
 #include <atomic>
@@ -47,6 +49,13 @@ struct Settings {
   bool enable_vad = false;
   std::string vad_model_filename = "ggml-silero-vad.bin";  // src/config.h:25
   float vad_threshold = 0.75f;                             // src/config.h:34
+  // Engine extension (whisper.cpp's params.vad): with enable_vad
+  // and a loaded VAD model, the clip's speech segments are cut out on the GPU
+  // (threshold = vad_threshold, the other mwx_vad_params at their defaults) and
+  // only they are decoded; times are reported on the clip's own timeline. A
+  // clip without segments gets the gate's empty result. Replaces the gate
+  // pass: a clip still goes through the VAD once.
+  bool vad_trim = false;
   int vad_ms_min_duration = 500;
   int n_threads = 4;
   int parallel_requests = 2;
@@ -72,6 +81,9 @@ struct Settings {
   int max_batch = 1;
   int batch_window_us = 2000;
 };
+
+// Owner of one mwx_vad_trimmed (vad_trim; defined in stt_engine.cpp).
+struct TrimmedAudio;
 
 struct TokenData {
   std::string text;
@@ -216,10 +228,12 @@ class SttEngine {
     double t_start_ms = 0.0, t_proc_ms = 0.0;
     int token_count = 0;
     std::vector<TranscriptionResult> results;
+    std::shared_ptr<TrimmedAudio> trimmed;  // vad_trim: the request's single-clip object
   };
   std::vector<TranscriptionResult> transcribe_batched(const std::vector<float>& pcmf32,
                                                       const RequestOptions& options,
-                                                      PerformanceMetrics* out_metrics);
+                                                      PerformanceMetrics* out_metrics,
+                                                      std::shared_ptr<TrimmedAudio> trimmed);
   void batcher_loop(std::vector<mwx_state*> states);
   std::string options_key(const RequestOptions& o) const;
   std::deque<std::shared_ptr<Pending>> queue_;
@@ -237,6 +251,13 @@ class SttEngine {
   std::vector<TranscriptionResult> collect(mwx_state* state, const std::string& lang,
                                            const float* pcm, size_t pcm_size,
                                            const ProsodyOptions& popts, int* token_count) const;
+
+  // vad_trim: VAD, segments and compaction of the clips in one pass under the
+  // VAD mutex; null when trimming is off or the call failed (the clips then
+  // take the untrimmed path)
+  std::shared_ptr<TrimmedAudio> trim_clips(const float* const* pcm, const int* n_samples,
+                                              int n_clips);
+  bool trim_active_ = false;  // vad_trim, a VAD context and a library that has the calls
 
   // the one result of a clip the VAD gate holds back (src/stt_engine.cpp:172-183)
   static TranscriptionResult empty_result(size_t pcm_size);

@@ -100,6 +100,13 @@ class VadContextParams(C.Structure):
     _fields_ = [("n_threads", C.c_int), ("use_gpu", C.c_bool), ("gpu_device", C.c_int)]
 
 
+class VadParams(C.Structure):
+    """mwx_vad_params (whisper_vad_params): the segment rule's parameters."""
+    _fields_ = [("threshold", C.c_float), ("min_speech_duration_ms", C.c_int),
+                ("min_silence_duration_ms", C.c_int), ("max_speech_duration_s", C.c_float),
+                ("speech_pad_ms", C.c_int), ("samples_overlap", C.c_float)]
+
+
 class ProsodyParams(C.Structure):
     """mwx_prosody_params = the reference's ProsodyOptions
     (src/prosody_extractor.h:21-27)."""
@@ -280,6 +287,46 @@ def lib() -> C.CDLL:
     L.mwx_vad_last_kernel_ms.argtypes = [P, fpp, fpp]
     L.mwx_write_synthetic_vad_model.restype = C.c_int
     L.mwx_write_synthetic_vad_model.argtypes = [C.c_char_p, C.c_uint64]
+    ip = C.POINTER(C.c_int)
+    L.mwx_vad_default_params.restype = VadParams
+    L.mwx_vad_default_params.argtypes = []
+    L.mwx_vad_segments_from_probs.restype = P
+    L.mwx_vad_segments_from_probs.argtypes = [P, VadParams]
+    L.mwx_vad_segments_from_samples.restype = P
+    L.mwx_vad_segments_from_samples.argtypes = [P, VadParams, C.c_void_p, C.c_int]
+    L.mwx_vad_segments_n_segments.restype = C.c_int
+    L.mwx_vad_segments_n_segments.argtypes = [P]
+    for n in ("t0", "t1"):
+        f = getattr(L, f"mwx_vad_segments_get_segment_{n}")
+        f.restype = C.c_float
+        f.argtypes = [P, C.c_int]
+    L.mwx_vad_free_segments.restype = None
+    L.mwx_vad_free_segments.argtypes = [P]
+    L.mwx_vad_trim_batch.restype = P
+    L.mwx_vad_trim_batch.argtypes = [P, VadParams, C.POINTER(C.c_void_p), ip, C.c_int]
+    L.mwx_vad_trimmed_n_clips.restype = C.c_int
+    L.mwx_vad_trimmed_n_clips.argtypes = [P]
+    L.mwx_vad_trimmed_n_segments.restype = C.c_int
+    L.mwx_vad_trimmed_n_segments.argtypes = [P, C.c_int]
+    L.mwx_vad_trimmed_segment.restype = C.c_int
+    L.mwx_vad_trimmed_segment.argtypes = [P, C.c_int, C.c_int, i64p, i64p]
+    L.mwx_vad_trimmed_n_samples.restype = C.c_int64
+    L.mwx_vad_trimmed_n_samples.argtypes = [P, C.c_int]
+    L.mwx_vad_trimmed_pcm.restype = C.c_void_p
+    L.mwx_vad_trimmed_pcm.argtypes = [P, C.c_int]
+    L.mwx_vad_trimmed_map_time.restype = C.c_int64
+    L.mwx_vad_trimmed_map_time.argtypes = [P, C.c_int, C.c_int64, C.c_bool]
+    L.mwx_vad_trimmed_free.restype = None
+    L.mwx_vad_trimmed_free.argtypes = [P]
+    L.mwx_vad_last_trim_kernel_ms.restype = C.c_int
+    L.mwx_vad_last_trim_kernel_ms.argtypes = [P, fpp, fpp]
+    L.mwx_full_batch_trimmed.restype = C.c_int
+    L.mwx_full_batch_trimmed.argtypes = [P, C.POINTER(P), FullParams, C.POINTER(P), ip, C.c_int]
+    L.mwx_test_vad_segments.restype = C.c_int
+    L.mwx_test_vad_segments.argtypes = [P, C.POINTER(VadParams), fpp, ip, ip, C.c_int, ip, i64p,
+                                        i64p, i64p, ip]
+    L.mwx_test_vad_trimmed_pcm.restype = C.c_int64
+    L.mwx_test_vad_trimmed_pcm.argtypes = [P, C.c_int, fpp, C.c_int64]
     _lib = L
     return L
 
@@ -498,6 +545,16 @@ class Context:
         ptrs = (C.POINTER(C.c_float) * n)(*[b.ptr for b in bufs])
         ln = (C.c_int * n)(*[b.n for b in bufs])
         return lib().mwx_full_batch(self.ctx, states, params, ptrs, ln, n)
+
+    def full_batch_trimmed(self, trimmed: Sequence["VadTrimmed"], clip_index: Sequence[int],
+                           params: FullParams, state0: int = 0) -> int:
+        """mwx_full_batch_trimmed: entry b = clip clip_index[b] of trimmed[b], on
+        state state0 + b; the getters then return times of the original clips."""
+        n = len(trimmed)
+        states = (C.c_void_p * n)(*[self.state(state0 + i) for i in range(n)])
+        objs = (C.c_void_p * n)(*[t.t for t in trimmed])
+        idx = (C.c_int * n)(*clip_index)
+        return lib().mwx_full_batch_trimmed(self.ctx, states, params, objs, idx, n)
 
     def segments(self, state_index: int = 0) -> List[Segment]:
         L = lib()
@@ -863,6 +920,135 @@ class VadContext:
         if lib().mwx_vad_last_kernel_ms(self.vctx, C.byref(a), C.byref(b)) != 0:
             raise RuntimeError("mwx_vad_last_kernel_ms: no timed call")
         return a.value, b.value
+
+    # ---- speech segments and trimming ----
+    @staticmethod
+    def _segments(handle) -> List[tuple]:
+        """[(t0, t1), ...] in centiseconds (float) of an mwx_vad_segments; frees it."""
+        L = lib()
+        if not handle:
+            raise RuntimeError("mwx_vad_segments_* failed")
+        try:
+            return [(L.mwx_vad_segments_get_segment_t0(handle, i),
+                     L.mwx_vad_segments_get_segment_t1(handle, i))
+                    for i in range(L.mwx_vad_segments_n_segments(handle))]
+        finally:
+            L.mwx_vad_free_segments(handle)
+
+    def segments_from_probs(self, params: Optional[VadParams] = None) -> List[tuple]:
+        """mwx_vad_segments_from_probs over the last detect()'s probabilities."""
+        return self._segments(lib().mwx_vad_segments_from_probs(self.vctx, params or vad_params()))
+
+    def segments_from_samples(self, pcm, params: Optional[VadParams] = None) -> List[tuple]:
+        _keep, addr, n = self._clip(pcm)
+        return self._segments(lib().mwx_vad_segments_from_samples(
+            self.vctx, params or vad_params(), addr, n))
+
+    def trim_batch(self, pcms, params: Optional[VadParams] = None) -> "VadTrimmed":
+        """mwx_vad_trim_batch: VAD, segments and compaction of every clip."""
+        clips = [self._clip(p) for p in pcms]
+        n = len(clips)
+        ptrs = (C.c_void_p * max(n, 1))(*[c[1] for c in clips])
+        lens = (C.c_int * max(n, 1))(*[c[2] for c in clips])
+        t = lib().mwx_vad_trim_batch(self.vctx, params or vad_params(), ptrs, lens, n)
+        if not t:
+            raise RuntimeError("mwx_vad_trim_batch failed")
+        return VadTrimmed(t)
+
+    def last_trim_kernel_ms(self):
+        """(segments, compaction) device milliseconds of the last trim_batch."""
+        a, b = C.c_float(), C.c_float()
+        if lib().mwx_vad_last_trim_kernel_ms(self.vctx, C.byref(a), C.byref(b)) != 0:
+            raise RuntimeError("mwx_vad_last_trim_kernel_ms: no timed call")
+        return a.value, b.value
+
+    def test_segments(self, probs: Sequence[np.ndarray], n_samples: Sequence[int],
+                      params: Sequence[VadParams]):
+        """mwx_test_vad_segments: vad_segments_kernel over given probabilities.
+        Per clip: (segments [(s, e)], pieces [(src, len, dst)], compacted length)."""
+        n = len(probs)
+        arrs = [np.ascontiguousarray(p, np.float32) for p in probs]
+        counts = [len(a) for a in arrs]
+        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        flat = np.concatenate(arrs + [np.zeros(1, np.float32)])
+        ns = np.ascontiguousarray(n_samples, np.int32)
+        prm = (VadParams * n)(*params)
+        nseg = np.zeros(n, np.int32)
+        clen = np.zeros(n, np.int64)
+        seg = np.zeros(2 * max(1, int(offs[-1])), np.int64)
+        pcs = np.zeros(3 * max(1, int(offs[-1])), np.int64)
+        ip, i64p = C.POINTER(C.c_int), C.POINTER(C.c_int64)
+        rc = lib().mwx_test_vad_segments(self.vctx, prm, fptr(flat), offs.ctypes.data_as(ip),
+                                         ns.ctypes.data_as(ip), n, nseg.ctypes.data_as(ip),
+                                         clen.ctypes.data_as(i64p), seg.ctypes.data_as(i64p),
+                                         pcs.ctypes.data_as(i64p), offs.ctypes.data_as(ip))
+        if rc != 0:
+            raise RuntimeError(f"mwx_test_vad_segments failed ({rc})")
+        out = []
+        for b in range(n):
+            o, m = int(offs[b]), int(nseg[b])
+            out.append(([tuple(int(v) for v in seg[2 * (o + k):2 * (o + k) + 2]) for k in range(m)],
+                        [tuple(int(v) for v in pcs[3 * (o + k):3 * (o + k) + 3]) for k in range(m)],
+                        int(clen[b])))
+        return out
+
+
+def vad_params(**kw) -> VadParams:
+    """mwx_vad_default_params with fields replaced."""
+    p = lib().mwx_vad_default_params()
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+class VadTrimmed:
+    """mwx_vad_trimmed: the speech segments of every clip of a trim_batch call
+    and the compacted PCM on the device. Independent of its VadContext."""
+
+    def __init__(self, handle):
+        self.t = handle
+
+    def free(self):
+        if self.t:
+            lib().mwx_vad_trimmed_free(self.t)
+            self.t = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+    def __len__(self):
+        return lib().mwx_vad_trimmed_n_clips(self.t)
+
+    def segments(self, clip: int) -> List[tuple]:
+        """[(start, end), ...] in samples of the caller's clip."""
+        L = lib()
+        out = []
+        for i in range(L.mwx_vad_trimmed_n_segments(self.t, clip)):
+            a, b = C.c_int64(), C.c_int64()
+            if L.mwx_vad_trimmed_segment(self.t, clip, i, C.byref(a), C.byref(b)) != 0:
+                raise RuntimeError("mwx_vad_trimmed_segment failed")
+            out.append((a.value, b.value))
+        return out
+
+    def n_samples(self, clip: int) -> int:
+        return lib().mwx_vad_trimmed_n_samples(self.t, clip)
+
+    def map_time(self, clip: int, t_cs: int, is_end: bool) -> int:
+        return lib().mwx_vad_trimmed_map_time(self.t, clip, t_cs, is_end)
+
+    def pcm(self, clip: int) -> np.ndarray:
+        """mwx_test_vad_trimmed_pcm: the compacted clip, copied to the host."""
+        n = self.n_samples(clip)
+        out = np.empty(max(n, 1), np.float32)
+        r = lib().mwx_test_vad_trimmed_pcm(self.t, clip, fptr(out), n)
+        if r != n:
+            raise RuntimeError(f"mwx_test_vad_trimmed_pcm returned {r}")
+        return out[:n].copy()
 
 
 def read_hparams(path: str) -> List[int]:
