@@ -119,11 +119,14 @@ int mwx_test_set_dec_shared(int on);
  * Returns the previous mode. */
 int mwx_test_set_gemm_8ph(int on);
 
-/* The decode LayerNorms before the QKV and cross-Q projections folded into
- * those split-K GEMMs at one row (gemm_splitk_ln, bit-identical to the
- * separate LayerNorm launch) on (1) / off (0) / back to the MWX_LN_FOLD
- * environment default, on (-1). Read when a decode step is captured. Returns
- * the previous mode. */
+/* The decode LayerNorms folded into the GEMM that consumes them: those before
+ * the QKV and cross-Q projections into the split-K GEMMs (gemm_splitk_ln) and
+ * the one before FFN1 into the full-K GEMM with the GELU epilogue
+ * (gemm_decode_ln), each bit-identical to the separate LayerNorm launch. The
+ * fold applies only to single-row decode steps that are not a prompt prefill;
+ * every other step launches the LayerNorms on their own whatever the mode.
+ * On (1) / off (0) / back to the MWX_LN_FOLD environment default, on (-1).
+ * Read when a decode step is captured. Returns the previous mode. */
 int mwx_test_set_ln_fold(int on);
 
 
@@ -148,6 +151,50 @@ long mwx_test_set_ra_mismatch(long step);
 int mwx_test_xattn_mx(struct mwx_context* ctx, int R, int H, int n, int nq, const float* q,
                       const uint8_t* k8, const uint8_t* ks, const uint8_t* v8, const uint8_t* vs,
                       float* o);
+
+/* One decode attention launch on given data, for an f64 reference at chosen
+ * positions (tests/test_gpu_decode_kernels.py). bf16 selects the kernels'
+ * weight / output type (bf16 or f16) whatever the context's model holds.
+ * fixed_len == 0: self-attention (dec_attention<T>, pcols = 3 H 64, row r
+ * attends positions 0 .. pos[r], appending its own); prefill != 0: kv_append<T>
+ * first, then dec_attention with write_new = 0. fixed_len > 0: cross-attention
+ * over fixed_len keys (pcols = H 64), by dec_attention<T>, or with grouped != 0
+ * by dec_cross_attention_grouped<T> on the f16 caches (nq 2..8, qscale 1).
+ *   P [KS][R][pcols] f32 split-K slabs, bias [pcols];
+ *   kcache / vcache [slots][H][cap][64] f16 bits, in and out (the caches as
+ *     they are after the launch);
+ *   kv_index [R] (nullable: row r uses slot r), pos [R] (self), active [R];
+ *   kvmap [R][cap] and own_from [R] (self, both or neither): position
+ *     j < own_from[r] of row r is read from slot kvmap[r][j] - map_row0;
+ *   o [R][H 64] f32 = the 16-bit output unpacked from the pack_index layout;
+ *     a row the launch did not write is NaN.
+ * Every index is checked on the host first: -1 without a launch unless
+ * R <= 1024, H <= 32, slots <= 64 (R <= slots without kv_index),
+ * KS in 1..8, nq in 1..8, R % nq == 0, cap <= 1536, fixed_len <= cap, and for
+ * every row (active or not) kv_index in [0, slots), pos < cap, own_from <= pos
+ * and each used kvmap word - map_row0 in [0, slots). Returns 0, -1 (arguments),
+ * -2 (device error) or -4 (group size the grouped kernel does not serve). */
+int mwx_test_dec_attn(struct mwx_context* ctx, int bf16, int grouped, int prefill, int R, int H,
+                      int cap, int slots, int KS, int nq, int fixed_len, const float* P,
+                      const float* bias, float qscale, float kscale, float scale,
+                      uint16_t* kcache, uint16_t* vcache, const int* kv_index, const int* pos,
+                      const int* active, const int* kvmap, const int* own_from, int map_row0,
+                      float* o);
+
+/* One decode GEMM on given 16-bit weights: a [M][K] and w [N][K] are rounded
+ * to bf16 (bf16 != 0) or f16 and packed as fragment tiles (pack_index; a
+ * zero-padded to a multiple of 64 rows, w to a multiple of 16 columns, as the
+ * engine's buffers are). mode 0: gemm_splitk_partials<T>, *ks_out = KS and
+ * out = the slabs P [KS][M][N] (room for 8 M N floats); mode 1: gemm_decode<T>
+ * with EPI_F32, out = c [M][N]; mode 2: gemm_decode<T> with EPI_RES, out =
+ * (a.w + bias[n]) + res[m][n] (bias nullable; modes 0 / 1 take neither).
+ * The device output starts as sentinel words between two guard bands of them.
+ * Returns 0, -1 (arguments; K % 32, M <= 512, N <= 4096, K <= 8192), -2
+ * (device error), -3 (the launch changed a guard band) or -4 (K not served by
+ * the kernel family). */
+int mwx_test_gemm_dec(struct mwx_context* ctx, int bf16, int mode, int M, int N, int K,
+                      const float* a, const float* w, const float* bias, const float* res,
+                      int* ks_out, float* out);
 
 /* vad_segments_kernel on caller-supplied probabilities: clip b has
  * mwx_vad_n_chunks(n_samples[b]) of them at probs + probs_offset[b] and its own

@@ -2527,3 +2527,194 @@ extern "C" int mwx_test_sample_draws(struct mwx_context* ctx, const float* probs
     return -2;
   }
 }
+
+// The decode attention launchers on given data (mwx_test_dec_attn): every
+// index the kernels form was checked by the caller below, so the launch stays
+// inside the buffers allocated here. The output buffer starts as all-ones
+// bits (NaN in f16 and bf16): a row the kernel does not write reads back NaN.
+template <typename T>
+static int test_dec_attn_impl(int grouped, int prefill, int R, int H, int cap, int slots, int KS,
+                              int nq, int fixed_len, const float* P, const float* bias,
+                              float qscale, float kscale, float scale, uint16_t* kc, uint16_t* vc,
+                              const int* kv_index, const int* pos, const int* active,
+                              const int* kvmap, const int* own_from, int map_row0, float* o) {
+  const int D = H * 64, pcols = fixed_len ? D : 3 * D;
+  const size_t R64 = (size_t)(R + 63) / 64 * 64;
+  const size_t pb = (size_t)KS * R * pcols * 4, cb = (size_t)slots * H * cap * 64 * 2;
+  DevScratch m;
+  void* dP = m.get(pb);
+  void* dbias = m.get((size_t)pcols * 4);
+  void* dk = m.get(cb);
+  void* dv = m.get(cb);
+  void* dkvi = kv_index ? m.get((size_t)R * 4) : nullptr;
+  void* dpos = m.get((size_t)R * 4);
+  void* dact = m.get((size_t)R * 4);
+  void* dmap = kvmap ? m.get((size_t)R * cap * 4) : nullptr;
+  void* down = own_from ? m.get((size_t)R * 4) : nullptr;
+  void* dout = m.get(R64 * D * sizeof(T));
+  HIPC(hipMemcpy(dP, P, pb, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(dbias, bias, (size_t)pcols * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(dk, kc, cb, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(dv, vc, cb, hipMemcpyHostToDevice));
+  if (dkvi) HIPC(hipMemcpy(dkvi, kv_index, (size_t)R * 4, hipMemcpyHostToDevice));
+  if (pos)
+    HIPC(hipMemcpy(dpos, pos, (size_t)R * 4, hipMemcpyHostToDevice));
+  else
+    HIPC(hipMemset(dpos, 0, (size_t)R * 4));
+  HIPC(hipMemcpy(dact, active, (size_t)R * 4, hipMemcpyHostToDevice));
+  if (dmap) HIPC(hipMemcpy(dmap, kvmap, (size_t)R * cap * 4, hipMemcpyHostToDevice));
+  if (down) HIPC(hipMemcpy(down, own_from, (size_t)R * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemset(dout, 0xff, R64 * D * sizeof(T)));
+  bool ok = true;
+  if (grouped) {
+    ok = mwx::dec_cross_attention_grouped<T>((const float*)dP, KS, pcols, (const float*)dbias, dk,
+                                             dv, (const int*)dkvi, (const int*)dact, fixed_len,
+                                             cap, (T*)dout, R, H, scale, nq, nullptr);
+  } else {
+    if (prefill)
+      mwx::kv_append<T>((const float*)dP, KS, pcols, (const float*)dbias, kscale, (_Float16*)dk,
+                        (_Float16*)dv, (const int*)dkvi, (const int*)dpos, (const int*)dact, cap,
+                        R, H, nullptr);
+    mwx::dec_attention<T>((const float*)dP, KS, pcols, (const float*)dbias, qscale, kscale,
+                          (_Float16*)dk, (_Float16*)dv, (const int*)dkvi, (const int*)dpos,
+                          (const int*)dact, fixed_len, cap, (T*)dout, R, H, scale, nullptr,
+                          (const int*)dmap, (const int*)down, map_row0, nq, prefill ? 0 : 1);
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  if (!ok) return -4;
+  std::vector<uint16_t> ob(R64 * D);
+  static_assert(sizeof(T) == 2, "16-bit output");
+  HIPC(hipMemcpy(ob.data(), dout, ob.size() * 2, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(kc, dk, cb, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(vc, dv, cb, hipMemcpyDeviceToHost));
+  const bool bf = std::is_same<T, __bf16>::value;
+  for (int r = 0; r < R; ++r)
+    for (int c = 0; c < D; ++c) {
+      const uint16_t b = ob[mwx::pack_index(r, c, D)];
+      o[(size_t)r * D + c] = bf ? mwx::bf16_to_f32(b) : mwx::f16_to_f32(b);
+    }
+  return 0;
+}
+
+extern "C" int mwx_test_dec_attn(struct mwx_context* ctx, int bf16, int grouped, int prefill,
+                                 int R, int H, int cap, int slots, int KS, int nq, int fixed_len,
+                                 const float* P, const float* bias, float qscale, float kscale,
+                                 float scale, uint16_t* kcache, uint16_t* vcache,
+                                 const int* kv_index, const int* pos, const int* active,
+                                 const int* kvmap, const int* own_from, int map_row0, float* o) {
+  if (!ctx || !P || !bias || !kcache || !vcache || !active || !o) return -1;
+  if (R < 1 || R > 1024 || H < 1 || H > 32 || cap < 1 || cap > 1536 || slots < 1 || slots > 64)
+    return -1;
+  if (KS < 1 || KS > 8 || nq < 1 || nq > 8 || R % nq) return -1;
+  if (fixed_len < 0 || fixed_len > cap || fixed_len > 1536) return -1;
+  const bool self = fixed_len == 0;
+  if (self && (!pos || grouped)) return -1;
+  if (!self && (prefill || kvmap || own_from)) return -1;
+  if ((kvmap == nullptr) != (own_from == nullptr)) return -1;
+  // the grouped kernel forms q = f16(sum + bias): no query scale
+  if (grouped && (nq < 2 || qscale != 1.0f)) return -1;
+  if (!kv_index && R > slots) return -1;
+  // every row, active or not: the kernels fetch a row's control words (and the
+  // self kernel its first position-map words) before the inactive-row exit
+  for (int r = 0; r < R; ++r) {
+    if (kv_index && (kv_index[r] < 0 || kv_index[r] >= slots)) return -1;
+    if (!self) continue;
+    if (pos[r] < 0 || pos[r] >= cap) return -1;
+    if (!own_from) continue;
+    if (own_from[r] < 0 || own_from[r] > pos[r]) return -1;
+    for (int j = 0; j < own_from[r]; ++j) {
+      const long s = (long)kvmap[(size_t)r * cap + j] - map_row0;
+      if (s < 0 || s >= slots) return -1;
+    }
+  }
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    if (bf16)
+      return test_dec_attn_impl<__bf16>(grouped, prefill, R, H, cap, slots, KS, nq, fixed_len, P,
+                                        bias, qscale, kscale, scale, kcache, vcache, kv_index, pos,
+                                        active, kvmap, own_from, map_row0, o);
+    return test_dec_attn_impl<_Float16>(grouped, prefill, R, H, cap, slots, KS, nq, fixed_len, P,
+                                        bias, qscale, kscale, scale, kcache, vcache, kv_index, pos,
+                                        active, kvmap, own_from, map_row0, o);
+  } catch (...) {
+    return -2;
+  }
+}
+
+// The decode GEMMs on given data (mwx_test_gemm_dec). The output lies between
+// two guard bands of sentinel words and starts as sentinel words itself, so a
+// store outside [M][N] (or one left out) shows.
+constexpr uint32_t TEST_GUARD_WORD = 0x7fc5a5a5u;  // a NaN no kernel produces
+constexpr size_t TEST_GUARD_WORDS = 1024;
+
+template <typename T>
+static int test_gemm_dec_impl(int mode, int M, int N, int K, const float* a, const float* w,
+                              const float* bias, const float* res, int* ks_out, float* out) {
+  const bool bf = std::is_same<T, __bf16>::value;
+  auto cvt = [&](float f) { return bf ? mwx::f32_to_bf16(f) : mwx::f32_to_f16(f); };
+  const size_t M64 = (size_t)(M + 63) / 64 * 64, N16 = (size_t)(N + 15) / 16 * 16;
+  std::vector<uint16_t> ap(M64 * K, 0), wp(N16 * K, 0);
+  for (int m = 0; m < M; ++m)
+    for (int k = 0; k < K; ++k) ap[mwx::pack_index(m, k, K)] = cvt(a[(size_t)m * K + k]);
+  for (int n = 0; n < N; ++n)
+    for (int k = 0; k < K; ++k) wp[mwx::pack_index(n, k, K)] = cvt(w[(size_t)n * K + k]);
+  const int ks_want = mode == 0 ? mwx::splitk_factor(K) : 1;
+  if (ks_want < 1 || ks_want > 8) return -4;
+  const size_t body = (size_t)ks_want * M * N, G = TEST_GUARD_WORDS, total = body + 2 * G;
+  std::vector<uint32_t> host(total, TEST_GUARD_WORD);
+  DevScratch m;
+  void* da = m.get(ap.size() * 2);
+  void* dw = m.get(wp.size() * 2);
+  void* dc = m.get(total * 4);
+  void* db = bias ? m.get((size_t)N * 4) : nullptr;
+  void* dr = res ? m.get((size_t)M * N * 4) : nullptr;
+  HIPC(hipMemcpy(da, ap.data(), ap.size() * 2, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(dw, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(dc, host.data(), total * 4, hipMemcpyHostToDevice));
+  if (db) HIPC(hipMemcpy(db, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+  if (dr) HIPC(hipMemcpy(dr, res, (size_t)M * N * 4, hipMemcpyHostToDevice));
+  float* c = (float*)dc + G;
+  const mwx::DecW<T> W((const T*)dw);
+  int ks = 1;
+  bool ok = true;
+  if (mode == 0) {
+    ks = mwx::gemm_splitk_partials<T>((const T*)da, W, M, N, K, c, nullptr);
+    ok = ks == ks_want;
+  } else {
+    mwx::EpiParams e;
+    e.c32 = c;
+    e.ldc = N;
+    if (mode == 2) {
+      e.bias = (const float*)db;
+      e.r32 = (const float*)dr;
+    }
+    ok = mwx::gemm_decode<T>(mode == 2 ? mwx::EPI_RES : mwx::EPI_F32, (const T*)da, W, M, N, K, e,
+                             nullptr);
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  if (!ok) return -4;
+  HIPC(hipMemcpy(host.data(), dc, total * 4, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < G; ++i)
+    if (host[i] != TEST_GUARD_WORD || host[G + body + i] != TEST_GUARD_WORD) return -3;
+  memcpy(out, host.data() + G, body * 4);
+  if (ks_out) *ks_out = ks;
+  return 0;
+}
+
+extern "C" int mwx_test_gemm_dec(struct mwx_context* ctx, int bf16, int mode, int M, int N, int K,
+                                 const float* a, const float* w, const float* bias,
+                                 const float* res, int* ks_out, float* out) {
+  if (!ctx || !a || !w || !out || mode < 0 || mode > 2) return -1;
+  if (M < 1 || M > 512 || N < 1 || N > 4096 || K < 32 || K > 8192 || K % 32) return -1;
+  if (mode == 2 && !res) return -1;
+  if (mode != 2 && (bias || res)) return -1;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    if (bf16) return test_gemm_dec_impl<__bf16>(mode, M, N, K, a, w, bias, res, ks_out, out);
+    return test_gemm_dec_impl<_Float16>(mode, M, N, K, a, w, bias, res, ks_out, out);
+  } catch (...) {
+    return -2;
+  }
+}

@@ -253,6 +253,13 @@ def lib() -> C.CDLL:
     L.mwx_test_sample_draws.argtypes = [P, fpp, fpp, C.c_int, C.c_int, C.POINTER(C.c_double),
                                         C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
                                         C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    ipp, u16p = C.POINTER(C.c_int), C.POINTER(C.c_uint16)
+    L.mwx_test_dec_attn.restype = C.c_int
+    L.mwx_test_dec_attn.argtypes = [P] + [C.c_int] * 10 + [fpp, fpp, C.c_float, C.c_float,
+                                                          C.c_float, u16p, u16p, ipp, ipp, ipp,
+                                                          ipp, ipp, C.c_int, fpp]
+    L.mwx_test_gemm_dec.restype = C.c_int
+    L.mwx_test_gemm_dec.argtypes = [P] + [C.c_int] * 5 + [fpp, fpp, fpp, fpp, ipp, fpp]
     L.mwx_resample_max_frames.restype = C.c_long
     L.mwx_resample_max_frames.argtypes = [C.c_int, C.c_int, C.c_int]
     L.mwx_resample.restype = C.c_int
@@ -800,6 +807,75 @@ class Context:
         if rc != 0:
             raise RuntimeError(f"mwx_test_xattn_mx failed ({rc})")
         return o
+
+    def test_dec_attn(self, P: np.ndarray, bias: np.ndarray, kcache: np.ndarray,
+                      vcache: np.ndarray, *, bf16: bool, active, pos=None, kv_index=None,
+                      fixed_len: int = 0, qscale: float = 1.0, kscale: float = 1.0,
+                      scale: float = 1.0, nq: int = 1, grouped: bool = False,
+                      prefill: bool = False, kvmap=None, own_from=None, map_row0: int = 0):
+        """mwx_test_dec_attn: one decode attention launch. P [KS][R][pcols] f32,
+        kcache / vcache [slots][H][cap][64] float16 (not modified). Returns
+        (o [R][H*64] f32, kcache after, vcache after); a row the launch did not
+        write is NaN in o. Raises ValueError when the hook refuses the indices."""
+        P = np.ascontiguousarray(P, dtype=np.float32)
+        bias = np.ascontiguousarray(bias, dtype=np.float32)
+        KS, R, pcols = P.shape
+        slots, H, cap, _ = kcache.shape
+        assert kcache.dtype == np.float16 and vcache.dtype == np.float16
+        assert vcache.shape == kcache.shape and kcache.shape[3] == 64
+        assert pcols == (H * 64 if fixed_len else 3 * H * 64) and bias.shape == (pcols,)
+        kc = np.array(kcache, dtype=np.float16, order="C").view(np.uint16)
+        vc = np.array(vcache, dtype=np.float16, order="C").view(np.uint16)
+        ip = C.POINTER(C.c_int)
+
+        def ints(a, shape):
+            if a is None:
+                return None, ip()
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            assert a.shape == shape, (a.shape, shape)
+            return a, a.ctypes.data_as(ip)
+
+        keep = [ints(active, (R,)), ints(pos, (R,)), ints(kv_index, (R,)),
+                ints(kvmap, (R, cap)), ints(own_from, (R,))]
+        o = np.empty((R, H * 64), np.float32)
+        u16 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint16))
+        rc = lib().mwx_test_dec_attn(self.ctx, int(bf16), int(grouped), int(prefill), R, H, cap,
+                                     slots, KS, nq, fixed_len, fptr(P), fptr(bias), qscale, kscale,
+                                     scale, u16(kc), u16(vc), keep[2][1], keep[1][1], keep[0][1],
+                                     keep[3][1], keep[4][1], map_row0, fptr(o))
+        if rc == -1:
+            raise ValueError("mwx_test_dec_attn refused its arguments")
+        if rc != 0:
+            raise RuntimeError(f"mwx_test_dec_attn failed ({rc})")
+        return o, kc.view(np.float16), vc.view(np.float16)
+
+    def test_gemm_dec(self, a: np.ndarray, w: np.ndarray, *, bf16: bool, mode: int,
+                      bias=None, res=None) -> np.ndarray:
+        """mwx_test_gemm_dec: a [M][K], w [N][K] f32 (rounded to bf16 / f16 by the
+        hook). mode 0: the split-K slabs [KS][M][N]; mode 1: c [M][N] (EPI_F32);
+        mode 2: (a.w + bias) + res (EPI_RES)."""
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        M, K = a.shape
+        N = w.shape[0]
+        assert w.shape == (N, K)
+        null = C.POINTER(C.c_float)()
+        if bias is not None:
+            bias = np.ascontiguousarray(bias, dtype=np.float32)
+            assert bias.shape == (N,)
+        if res is not None:
+            res = np.ascontiguousarray(res, dtype=np.float32)
+            assert res.shape == (M, N)
+        out = np.empty((8 if mode == 0 else 1, M, N), np.float32)
+        ks = C.c_int(0)
+        rc = lib().mwx_test_gemm_dec(self.ctx, int(bf16), mode, M, N, K, fptr(a), fptr(w),
+                                     null if bias is None else fptr(bias),
+                                     null if res is None else fptr(res), C.byref(ks), fptr(out))
+        if rc == -1:
+            raise ValueError("mwx_test_gemm_dec refused its arguments")
+        if rc != 0:
+            raise RuntimeError(f"mwx_test_gemm_dec failed ({rc})")
+        return out[:ks.value].copy() if mode == 0 else out[0]
 
     def test_decode_last(self, tokens: Sequence[int], out: Optional[np.ndarray] = None,
                          state_index: int = 0) -> np.ndarray:

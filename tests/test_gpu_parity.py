@@ -894,11 +894,11 @@ def test_runahead_mismatch_falls_back_to_host_loop(rich, beam, fault_step, ladde
     monkeypatch.setenv("MWX_NO_RUNAHEAD", "1")
     host, n0 = run()
     monkeypatch.delenv("MWX_NO_RUNAHEAD")
-    mwx.set_ra_mismatch(fault_step)
+    prev = mwx.set_ra_mismatch(fault_step)
     try:
         redone, n1 = run()
     finally:
-        mwx.set_ra_mismatch(-1)
+        mwx.set_ra_mismatch(prev)
     print(f"beam {beam}, fault at step {fault_step}: {n1} attempt(s) redone on the host loop, "
           f"{sum(len(x) for x in host)} tokens")
     assert n0 == 0 and n1 >= 1
