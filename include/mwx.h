@@ -29,6 +29,11 @@
  * batched GPU pass (the data-parallel unit of this engine), and
  * mwx_write_synthetic_model writes a seeded model in the ggml .bin layout that
  * src/model_manager.cpp provisions (no real checkpoints exist offline).
+ * whisper_context_params.dtw_token_timestamps / dtw_aheads_preset / dtw_n_top /
+ * dtw_aheads / dtw_mem_size map to the mwx_context_params fields of the same
+ * names, whisper_aheads / whisper_ahead / whisper_alignment_heads_preset to
+ * mwx_aheads / mwx_ahead / mwx_alignment_heads_preset, and
+ * whisper_token_data.t_dtw to mwx_token_data.t_dtw.
  * The whisper_vad_* family (src/stt_engine.cpp:44-55, :108-115) maps to
  * mwx_vad_*: see the voice-activity section below. whisper_vad_segments_* and
  * whisper_full's params.vad map to mwx_vad_segments_*, mwx_vad_trim_batch and
@@ -74,6 +79,16 @@ enum mwx_log_level {
 typedef void (*mwx_log_callback)(enum mwx_log_level level, const char* text,
                                  void* user_data);
 
+/* whisper_ahead / whisper_aheads: one alignment head, a list of them */
+struct mwx_ahead {
+  int n_text_layer;
+  int n_head;
+};
+struct mwx_aheads {
+  size_t n_heads;
+  const struct mwx_ahead* heads;
+};
+
 struct mwx_context_params {
   bool use_gpu;     /* must be true: the engine has no CPU path */
   bool flash_attn;  /* accepted for API parity; attention is always fused */
@@ -83,6 +98,42 @@ struct mwx_context_params {
    * load, activations by the producer step) with gfx950's block-scaled fp8
    * MFMA. MWX_COMPUTE_MODEL (default) computes in the model's 16-bit type. */
   int compute;
+  /* DTW token timestamps (whisper.h dtw_token_timestamps and the fields after
+   * it): when set, mwx_token_data.t_dtw of every text token of every emitted
+   * segment is the time (10-ms units, the clip's timeline, like t0 / t1) a
+   * dynamic-time-warping path through the alignment heads' cross-attention
+   * assigns to it; otherwise t_dtw is -1. The rule is this project's
+   * definition (a teacher-forced pass per 30-s window after its
+   * result is final, HF transformers' normalisation, median filter and DTW).
+   * Ids, text, t0 / t1, p and plog do not depend on the setting.
+   * dtw_aheads_preset: enum mwx_alignment_heads_preset. N_TOP_MOST takes every
+   * head of the last dtw_n_top decoder layers (1 .. n_text_layer); CUSTOM the
+   * dtw_aheads list (n_text_layer = decoder layer, n_head = head); the model
+   * presets name a fixed list and require the model's geometry. Init fails on
+   * a layer or head outside the model. dtw_mem_size is accepted and unused. */
+  bool dtw_token_timestamps;
+  int dtw_aheads_preset;
+  int dtw_n_top;
+  struct mwx_aheads dtw_aheads;
+  size_t dtw_mem_size;
+};
+/* whisper_alignment_heads_preset (same order) */
+enum mwx_alignment_heads_preset {
+  MWX_AHEADS_NONE = 0,
+  MWX_AHEADS_N_TOP_MOST,
+  MWX_AHEADS_CUSTOM,
+  MWX_AHEADS_TINY_EN,
+  MWX_AHEADS_TINY,
+  MWX_AHEADS_BASE_EN,
+  MWX_AHEADS_BASE,
+  MWX_AHEADS_SMALL_EN,
+  MWX_AHEADS_SMALL,
+  MWX_AHEADS_MEDIUM_EN,
+  MWX_AHEADS_MEDIUM,
+  MWX_AHEADS_LARGE_V1,
+  MWX_AHEADS_LARGE_V2,
+  MWX_AHEADS_LARGE_V3,
+  MWX_AHEADS_LARGE_V3_TURBO,
 };
 enum mwx_compute {
   MWX_COMPUTE_MODEL = 0,
@@ -106,7 +157,7 @@ typedef struct mwx_token_data {
   float ptsum;   /* sum of probabilities of all timestamp tokens */
   int64_t t0;    /* token-level timestamps (10 ms units), -1 if unset */
   int64_t t1;
-  int64_t t_dtw;
+  int64_t t_dtw; /* DTW timestamp (mwx_context_params.dtw_token_timestamps), else -1 */
   float vlen; /* voice length of the token */
 } mwx_token_data;
 

@@ -212,6 +212,58 @@ int mwx_test_vad_segments(struct mwx_vad_context* vctx, const struct mwx_vad_par
 int64_t mwx_test_vad_trimmed_pcm(const struct mwx_vad_trimmed* t, int clip, float* out,
                                  int64_t cap);
 
+/* --- DTW token timestamps (mwx_context_params.dtw_token_timestamps) -------- */
+
+/* align_qk_kernel on given data: for every row r with active[r] and
+ * pos[r] >= pos0, and every pair heads[i] = (head, a), the softmax over n_keys
+ * keys of scale * q.k, q = f16((sum of the KS slabs of P [KS][R][H 64] +
+ * bias [H 64]) * qscale), keys of slot kv_index[r]. k: f16 bits
+ * [slots][H][n_keys][64], or with mx != 0 e4m3 codes in that shape with kscale
+ * [slots][H][n_keys][2] E8M0 (one per 32-element half), widened as the grouped
+ * cross-attention widens them. The cross cache is f16 (or MX) for f16 and
+ * bf16 models alike, so there is no bf16 variant. out
+ * [slots][A][n_rows_cap][n_keys] f32, in and out: row (kv_index[r], a,
+ * pos[r] - pos0) is written, every other word keeps what the caller put there.
+ * Indices are checked on the host: -1 without a launch. 0, -1, -2 (device
+ * error) or -4 (shape the kernel does not serve). */
+int mwx_test_align_probs(struct mwx_context* ctx, int mx, int R, int H, int KS, int n_keys,
+                         int slots, int n_heads, const int* heads, int A, int pos0,
+                         int n_rows_cap, const float* P, const float* bias, float qscale,
+                         float scale, const void* k, const uint8_t* kscale, const int* kv_index,
+                         const int* pos, const int* active, float* out);
+
+/* dtw_cost_kernel: w [B][A][n_rows_cap][n_keys] probabilities, clip b uses
+ * rows 0 .. Ns[b]-1 and columns 0 .. Ts[b]-1; cost: clip b's [Ns[b]][Ts[b]]
+ * matrix (rows compact) at cost + b * n_rows_cap * max(Ts). */
+int mwx_test_dtw_cost(struct mwx_context* ctx, int B, int A, int n_rows_cap, int n_keys,
+                      const int* Ns, const int* Ts, const float* w, float* cost);
+
+/* dtw_path_kernel on B cost matrices in one launch: clip b's [Ns[b]][Ts[b]]
+ * matrix (rows compact) at cost + b * max(Ns) * max(Ts). frames [B][max(Ns)]:
+ * the path's first column in each row; path [B][max(Ns) + max(Ts)][2]: the
+ * path's (row, column) pairs in order, right-aligned, path_len[b] of them.
+ * Ns <= 256, Ts <= 1536. */
+int mwx_test_dtw_path(struct mwx_context* ctx, int B, const int* Ns, const int* Ts,
+                      const float* cost, int* frames, int* path, int* path_len);
+
+/* A state keeps (on != 0) the results of every DTW pass of its next
+ * mwx_full* calls on the host: one pass per 30-s window that emitted
+ * segments. Returns the previous setting. */
+int mwx_test_dtw_keep(struct mwx_state* state, int on);
+int mwx_test_dtw_n_passes(struct mwx_state* state);
+/* Pass `pass` of the state's last call: dims = {N, T, A, n_audio_ctx}, the
+ * window's seek, probs [A][N][n_audio_ctx], cost [N][T], frames [N] (each
+ * nullable; *_cap = room in elements). */
+int mwx_test_dtw_last(struct mwx_state* state, int pass, int* dims, int64_t* seek, float* probs,
+                      long probs_cap, float* cost, long cost_cap, int* frames, long frames_cap);
+
+/* The DTW alignment pass (teacher-forced, positions 0 .. n-1, the alignment
+ * rows from pos0 on, n_cols columns) over the cross K/V that mwx_test_encode
+ * left in `state`, in a context with DTW on; the result is pass 0 of
+ * mwx_test_dtw_last. Returns 0 or < 0. */
+int mwx_test_dtw_align(struct mwx_context* ctx, struct mwx_state* state, const int* tokens, int n,
+                       int pos0, int n_cols);
+
 #ifdef __cplusplus
 }
 #endif

@@ -386,7 +386,10 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
   const Vocab& vb = C.vocab;
   const int V = hp.n_vocab;
   hipStream_t st = S.stream;
-  for (int c = 0; c < n_clips; ++c) states[c]->s.result_all.clear();
+  for (int c = 0; c < n_clips; ++c) {
+    states[c]->s.result_all.clear();
+    states[c]->s.dtw_dump.clear();
+  }
   if (P.audio_ctx > hp.n_audio_ctx) return -5;
   if (P.audio_ctx > 0 && P.audio_ctx != hp.n_audio_ctx) {
     MWX_LOG_ERROR("mwx: audio_ctx < n_audio_ctx is not supported\n");
@@ -1270,9 +1273,16 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
     // a clip's segments stay in order (its TsState carries from one to the
     // next), each token's energy sums stay sequential (same floats)
     std::vector<std::vector<size_t>> ts_todo(P.token_timestamps ? n_clips : 0);
+    // DTW token timestamps: the window's seek and first segment per clip
+    std::vector<int64_t> dtw_seek(C.dtw ? n_clips : 0);
+    std::vector<size_t> dtw_seg0(C.dtw ? n_clips : 0);
     for (int c : act) {
       ClipRun& cr = clips[c];
       State& cs = *cr.st;
+      if (C.dtw) {
+        dtw_seek[c] = cr.seek;
+        dtw_seg0[c] = cs.result_all.size();
+      }
       const Row& best = best_row[c];
       const int seek_delta = best.seek_delta;
       const int result_len = best.result_len;
@@ -1356,9 +1366,146 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
         for (auto& t : th) t.join();
       }
     }
+    // DTW token timestamps (DESIGN.md D8): one alignment pass over the windows
+    // that emitted segments. It runs after the window's result is final, on
+    // its own self cache, and only writes t_dtw: nothing else of the result
+    // (or of the next window's decode) depends on it
+    if (C.dtw) {
+      std::vector<typename Driver<T>::DtwClip> dc;
+      std::vector<State*> dst;
+      std::vector<int64_t> dsk;
+      for (int c : act) {
+        State& cs = *clips[c].st;
+        if (dtw_seg0[c] >= cs.result_all.size()) continue;
+        typename Driver<T>::DtwClip x;
+        x.slot = c;
+        x.tokens = clips[c].prompt_init;
+        if (P.no_timestamps) x.tokens.pop_back();  // (its NOT: the first alignment row)
+        x.pos0 = (int)x.tokens.size();
+        x.tokens.push_back(vb.token_not);
+        for (size_t si = dtw_seg0[c]; si < cs.result_all.size(); ++si)
+          for (const auto& td : cs.result_all[si].tokens)
+            if (td.id < vb.token_eot) x.tokens.push_back(td.id);
+        x.tokens.push_back(vb.token_eot);
+        x.n_rows = (int)x.tokens.size() - x.pos0;
+        if (x.n_rows <= 2 || (int)x.tokens.size() > D.Tctx || x.n_rows > DTW_MAX_ROWS) continue;
+        const int rem = (int)(clips[c].seek_end - dtw_seek[c]);
+        x.n_cols = std::max(1, std::min(P.audio_ctx > 0 ? P.audio_ctx : hp.n_audio_ctx, (rem + 1) / 2));
+        dc.push_back(std::move(x));
+        dst.push_back(&cs);
+        dsk.push_back(dtw_seek[c]);
+      }
+      if (!dc.empty()) {
+        if (aborted(P)) return -9;
+        D.dtw_pass(dc, dst, dsk.data());
+        for (size_t i = 0; i < dc.size(); ++i) {
+          State& cs = *dst[i];
+          int row = 1;  // (row 0 = NOT)
+          for (size_t si = dtw_seg0[dc[i].slot]; si < cs.result_all.size(); ++si)
+            for (auto& td : cs.result_all[si].tokens)
+              if (td.id < vb.token_eot) td.t_dtw = dsk[i] + 2 * (int64_t)dc[i].frames[row++];
+        }
+      }
+    }
   }
   for (int c = 0; c < n_clips; ++c) states[c]->s.lang_id = clips[c].lang_id;
   return 0;
+}
+
+// DTW token timestamps: the alignment heads of a context
+// (mwx_context_params.dtw_*). The presets are whisper.cpp's g_aheads tables
+// (INTEGRATION.md: unpinned) with the decoder geometry they were made for.
+struct AheadsPreset {
+  int preset, n_text_layer, n_text_head;
+  std::vector<mwx_ahead> heads;
+};
+static const std::vector<AheadsPreset>& aheads_presets() {
+  static const std::vector<AheadsPreset> t = {
+      {MWX_AHEADS_TINY_EN, 4, 6, {{1, 0}, {2, 0}, {2, 5}, {3, 0}, {3, 1}, {3, 2}, {3, 3}, {3, 4}}},
+      {MWX_AHEADS_TINY, 4, 6, {{2, 2}, {3, 0}, {3, 2}, {3, 3}, {3, 4}, {3, 5}}},
+      {MWX_AHEADS_BASE_EN, 6, 8, {{3, 3}, {4, 7}, {5, 1}, {5, 5}, {5, 7}}},
+      {MWX_AHEADS_BASE, 6, 8, {{3, 1}, {4, 2}, {4, 3}, {4, 7}, {5, 1}, {5, 2}, {5, 4}, {5, 6}}},
+      {MWX_AHEADS_SMALL_EN, 12, 12,
+       {{6, 6}, {7, 0}, {7, 3}, {7, 8}, {8, 2}, {8, 5}, {8, 7}, {9, 0}, {9, 4}, {9, 8}, {9, 10},
+        {10, 0}, {10, 1}, {10, 2}, {10, 3}, {10, 6}, {10, 11}, {11, 2}, {11, 4}}},
+      {MWX_AHEADS_SMALL, 12, 12,
+       {{5, 3}, {5, 9}, {8, 0}, {8, 4}, {8, 7}, {8, 8}, {9, 0}, {9, 7}, {9, 9}, {10, 5}}},
+      {MWX_AHEADS_MEDIUM_EN, 24, 16,
+       {{11, 4}, {14, 1}, {14, 12}, {14, 14}, {15, 4}, {16, 0}, {16, 4}, {16, 9}, {17, 12},
+        {17, 14}, {18, 7}, {18, 10}, {18, 15}, {20, 0}, {20, 3}, {20, 9}, {20, 14}, {21, 12}}},
+      {MWX_AHEADS_MEDIUM, 24, 16, {{13, 15}, {15, 4}, {15, 15}, {16, 1}, {20, 0}, {23, 4}}},
+      {MWX_AHEADS_LARGE_V1, 32, 20,
+       {{9, 19}, {11, 2}, {11, 4}, {11, 17}, {22, 7}, {22, 11}, {22, 17}, {23, 2}, {23, 15}}},
+      {MWX_AHEADS_LARGE_V2, 32, 20,
+       {{10, 12}, {13, 17}, {16, 11}, {16, 12}, {16, 13}, {17, 15}, {17, 16}, {18, 4}, {18, 11},
+        {18, 19}, {19, 11}, {21, 2}, {21, 3}, {22, 3}, {22, 9}, {22, 12}, {23, 5}, {23, 7},
+        {23, 13}, {25, 5}, {26, 1}, {26, 12}, {27, 15}}},
+      {MWX_AHEADS_LARGE_V3, 32, 20,
+       {{7, 0}, {10, 17}, {12, 18}, {13, 12}, {16, 1}, {17, 14}, {19, 11}, {21, 4}, {24, 1},
+        {25, 6}}},
+      {MWX_AHEADS_LARGE_V3_TURBO, 4, 20, {{2, 4}, {2, 11}, {3, 3}, {3, 6}, {3, 11}, {3, 14}}},
+  };
+  return t;
+}
+
+static bool dtw_setup(Context& C, const mwx_context_params& params) {
+  const int L = C.hp.n_text_layer, H = C.hp.n_text_head;
+  std::vector<mwx_ahead> heads;
+  const int preset = params.dtw_aheads_preset;
+  if (preset == MWX_AHEADS_N_TOP_MOST) {
+    if (params.dtw_n_top < 1 || params.dtw_n_top > L) {
+      MWX_LOG_ERROR("mwx: dtw_n_top %d outside 1..%d\n", params.dtw_n_top, L);
+      return false;
+    }
+    for (int l = L - params.dtw_n_top; l < L; ++l)
+      for (int h = 0; h < H; ++h) heads.push_back({l, h});
+  } else if (preset == MWX_AHEADS_CUSTOM) {
+    if (params.dtw_aheads.n_heads < 1 || !params.dtw_aheads.heads) {
+      MWX_LOG_ERROR("mwx: dtw_aheads_preset CUSTOM without alignment heads\n");
+      return false;
+    }
+    heads.assign(params.dtw_aheads.heads, params.dtw_aheads.heads + params.dtw_aheads.n_heads);
+  } else {
+    const AheadsPreset* ap = nullptr;
+    for (const auto& a : aheads_presets())
+      if (a.preset == preset) ap = &a;
+    if (!ap) {
+      MWX_LOG_ERROR("mwx: dtw_token_timestamps needs an alignment heads preset (got %d)\n", preset);
+      return false;
+    }
+    if (ap->n_text_layer != L || ap->n_text_head != H) {
+      MWX_LOG_ERROR("mwx: alignment heads preset %d is for %d layers x %d heads, the model has "
+                    "%d x %d\n", preset, ap->n_text_layer, ap->n_text_head, L, H);
+      return false;
+    }
+    heads = ap->heads;
+  }
+  for (const mwx_ahead& a : heads)
+    if (a.n_text_layer < 0 || a.n_text_layer >= L || a.n_head < 0 || a.n_head >= H) {
+      MWX_LOG_ERROR("mwx: alignment head (layer %d, head %d) outside the model (%d x %d)\n",
+                    a.n_text_layer, a.n_head, L, H);
+      return false;
+    }
+  C.dtw_heads.clear();
+  for (const mwx_ahead& a : heads) C.dtw_heads.emplace_back(a.n_text_layer, a.n_head);
+  C.dtw_off.assign(L, 0);
+  C.dtw_cnt.assign(L, 0);
+  std::vector<int2> dev;
+  for (int l = 0; l < L; ++l) {
+    C.dtw_off[l] = (int)dev.size();
+    for (size_t a = 0; a < heads.size(); ++a)
+      if (heads[a].n_text_layer == l) dev.push_back(int2{heads[a].n_head, (int)a});
+    C.dtw_cnt[l] = (int)dev.size() - C.dtw_off[l];
+  }
+  std::lock_guard<std::recursive_mutex> lock(capture_mutex());  // (legacy-stream copy)
+  if (hipMalloc((void**)&C.dtw_dev, dev.size() * sizeof(int2)) != hipSuccess ||
+      hipMemcpy(C.dtw_dev, dev.data(), dev.size() * sizeof(int2), hipMemcpyHostToDevice) !=
+          hipSuccess) {
+    MWX_LOG_ERROR("mwx: alignment heads upload failed\n");
+    return false;
+  }
+  C.dtw = true;
+  return true;
 }
 
 }  // namespace mwx
@@ -1377,6 +1524,12 @@ struct mwx_context_params mwx_context_default_params(void) {
   p.flash_attn = true;
   p.gpu_device = 0;
   p.compute = MWX_COMPUTE_MODEL;
+  p.dtw_token_timestamps = false;
+  p.dtw_aheads_preset = MWX_AHEADS_NONE;
+  p.dtw_n_top = -1;
+  p.dtw_aheads.n_heads = 0;
+  p.dtw_aheads.heads = nullptr;
+  p.dtw_mem_size = 1024 * 1024 * 128;
   return p;
 }
 
@@ -1426,6 +1579,10 @@ struct mwx_context* mwx_init_from_file_with_params(const char* path,
       auto f = C.vocab.token_to_id.find(s);
       if (f != C.vocab.token_to_id.end()) C.nst_ids.push_back(f->second);
     }
+    if (params.dtw_token_timestamps && !mwx::dtw_setup(C, params)) {
+      mwx_free(ctx);
+      return nullptr;
+    }
     return ctx;
   } catch (...) {
     return nullptr;
@@ -1467,7 +1624,9 @@ void mwx_free_state(struct mwx_state* state) {
                        &S.rs_in, &S.rs_out, &S.rs_pos, &S.rs_coef, &S.rrun, &S.rprompt, &S.meld, &S.melpart,
                        &S.melc_pcm[0], &S.melc_pcm[1], &S.melc_raw[0], &S.melc_raw[1],
                        &S.pf_in, &S.pf_x, &S.pf_h, &S.pf_o, &S.pf_ff, &S.pf_pqkv,
-                       &S.pf_pres, &S.pf_pq, &S.perf_span};
+                       &S.pf_pres, &S.pf_pq, &S.perf_span,
+                       &S.dtw_kself, &S.dtw_vself, &S.dtw_w, &S.dtw_cost, &S.dtw_frames,
+                       &S.dtw_meta};
   for (auto* b : bufs) b->release();
   if (S.pin) (void)hipHostFree(S.pin);
   S.pin = nullptr;
@@ -1494,6 +1653,7 @@ void mwx_free(struct mwx_context* ctx) {
   (void)hipSetDevice(ctx->c.device);
   if (ctx->c.arena) (void)hipFree(ctx->c.arena);
   if (ctx->c.gelu_tab) (void)hipFree(ctx->c.gelu_tab);
+  if (ctx->c.dtw_dev) (void)hipFree(ctx->c.dtw_dev);
   delete ctx;
 }
 
@@ -1623,6 +1783,7 @@ int mwx_full_batch_trimmed(struct mwx_context* ctx, struct mwx_state* const* sta
       for (auto& td : sg.tokens) {
         td.t0 = mwx::vad_map_time(*run_clips[r], td.t0, false);
         td.t1 = mwx::vad_map_time(*run_clips[r], td.t1, true);
+        if (td.t_dtw >= 0) td.t_dtw = mwx::vad_map_time(*run_clips[r], td.t_dtw, false);
       }
     }
   return 0;
@@ -2714,6 +2875,235 @@ extern "C" int mwx_test_gemm_dec(struct mwx_context* ctx, int bf16, int mode, in
     HIPC(hipSetDevice(ctx->c.device));
     if (bf16) return test_gemm_dec_impl<__bf16>(mode, M, N, K, a, w, bias, res, ks_out, out);
     return test_gemm_dec_impl<_Float16>(mode, M, N, K, a, w, bias, res, ks_out, out);
+  } catch (...) {
+    return -2;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// DTW token timestamps: the three kernels on given data, and a state's passes
+// ---------------------------------------------------------------------------
+extern "C" int mwx_test_align_probs(struct mwx_context* ctx, int mx, int R, int H, int KS,
+                                    int n_keys, int slots, int n_heads, const int* heads, int A,
+                                    int pos0, int n_rows_cap, const float* P, const float* bias,
+                                    float qscale, float scale, const void* k,
+                                    const uint8_t* kscale, const int* kv_index, const int* pos,
+                                    const int* active, float* out) {
+  if (!ctx || !heads || !P || !bias || !k || !kv_index || !pos || !active || !out) return -1;
+  if (mx && !kscale) return -1;
+  if (R < 1 || R > 1024 || H < 1 || H > 32 || KS < 1 || KS > 8 || n_keys < 1 ||
+      n_keys > mwx::DTW_MAX_KEYS || slots < 1 || slots > 64 || n_heads < 1 || n_heads > 64 ||
+      A < 1 || A > 64 || n_rows_cap < 1 || n_rows_cap > mwx::DTW_MAX_ROWS)
+    return -1;
+  for (int i = 0; i < n_heads; ++i)
+    if (heads[2 * i] < 0 || heads[2 * i] >= H || heads[2 * i + 1] < 0 || heads[2 * i + 1] >= A)
+      return -1;
+  for (int r = 0; r < R; ++r)
+    if (kv_index[r] < 0 || kv_index[r] >= slots) return -1;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    const int D = H * 64;
+    const size_t pb = (size_t)KS * R * D * 4, kb = (size_t)slots * H * n_keys * 64 * (mx ? 1 : 2),
+                 sb = (size_t)slots * H * n_keys * 2, ob = (size_t)slots * A * n_rows_cap * n_keys * 4;
+    DevScratch m;
+    void* dP = m.get(pb);
+    void* dbias = m.get((size_t)D * 4);
+    void* dk = m.get(kb);
+    void* dks = mx ? m.get(sb) : nullptr;
+    void* dkvi = m.get((size_t)R * 4);
+    void* dpos = m.get((size_t)R * 4);
+    void* dact = m.get((size_t)R * 4);
+    void* dh = m.get((size_t)n_heads * 8);
+    void* dout = m.get(ob);
+    HIPC(hipMemcpy(dP, P, pb, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dbias, bias, (size_t)D * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dk, k, kb, hipMemcpyHostToDevice));
+    if (dks) HIPC(hipMemcpy(dks, kscale, sb, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dkvi, kv_index, (size_t)R * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dpos, pos, (size_t)R * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dact, active, (size_t)R * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dh, heads, (size_t)n_heads * 8, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dout, out, ob, hipMemcpyHostToDevice));
+    const bool ok = mwx::align_probs((const float*)dP, KS, D, (const float*)dbias, qscale, scale, dk,
+                                     (const uint8_t*)dks, (const int*)dkvi, (const int*)dpos,
+                                     (const int*)dact, (const int2*)dh, n_heads, n_keys, n_keys, R,
+                                     H, pos0, A, n_rows_cap, (float*)dout, nullptr);
+    if (!ok) return -4;
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost));
+    return 0;
+  } catch (...) {
+    return -2;
+  }
+}
+
+static bool dtw_test_shapes(int B, const int* Ns, const int* Ts, int n_cap, int t_cap, int* n_max,
+                            int* t_max) {
+  if (B < 1 || B > 64 || !Ns || !Ts) return false;
+  *n_max = *t_max = 0;
+  for (int b = 0; b < B; ++b) {
+    if (Ns[b] < 1 || Ns[b] > n_cap || Ts[b] < 1 || Ts[b] > t_cap) return false;
+    *n_max = std::max(*n_max, Ns[b]);
+    *t_max = std::max(*t_max, Ts[b]);
+  }
+  return true;
+}
+
+extern "C" int mwx_test_dtw_cost(struct mwx_context* ctx, int B, int A, int n_rows_cap, int n_keys,
+                                 const int* Ns, const int* Ts, const float* w, float* cost) {
+  int n_max = 0, t_max = 0;
+  if (!ctx || !w || !cost || A < 1 || A > 1024 || n_rows_cap < 1 ||
+      n_rows_cap > mwx::DTW_MAX_ROWS || n_keys < 1 || n_keys > mwx::DTW_MAX_KEYS ||
+      !dtw_test_shapes(B, Ns, Ts, n_rows_cap, n_keys, &n_max, &t_max))
+    return -1;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    const size_t wb = (size_t)B * A * n_rows_cap * n_keys * 4;
+    const long cstride = (long)n_rows_cap * t_max;
+    DevScratch m;
+    void* dw = m.get(wb);
+    int* dmeta = (int*)m.get((size_t)3 * B * 4);
+    void* dc = m.get((size_t)B * cstride * 4);
+    std::vector<int> hm(3 * B);
+    for (int b = 0; b < B; ++b) {
+      hm[b] = b;
+      hm[B + b] = Ns[b];
+      hm[2 * B + b] = Ts[b];
+    }
+    HIPC(hipMemcpy(dw, w, wb, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dmeta, hm.data(), hm.size() * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemset(dc, 0xff, (size_t)B * cstride * 4));
+    if (!mwx::dtw_cost((const float*)dw, dmeta, dmeta + B, dmeta + 2 * B, B, A, n_rows_cap, n_keys,
+                       t_max, cstride, (float*)dc, nullptr))
+      return -4;
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(cost, dc, (size_t)B * cstride * 4, hipMemcpyDeviceToHost));
+    return 0;
+  } catch (...) {
+    return -2;
+  }
+}
+
+extern "C" int mwx_test_dtw_path(struct mwx_context* ctx, int B, const int* Ns, const int* Ts,
+                                 const float* cost, int* frames, int* path, int* path_len) {
+  int n_max = 0, t_max = 0;
+  if (!ctx || !cost || !frames || !path || !path_len ||
+      !dtw_test_shapes(B, Ns, Ts, mwx::DTW_MAX_ROWS, mwx::DTW_MAX_KEYS, &n_max, &t_max))
+    return -1;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    const long cstride = (long)n_max * t_max;
+    const int pcap = n_max + t_max;
+    DevScratch m;
+    void* dc = m.get((size_t)B * cstride * 4);
+    int* dmeta = (int*)m.get((size_t)2 * B * 4);
+    void* df = m.get((size_t)B * n_max * 4);
+    void* dp = m.get((size_t)B * pcap * 8);
+    void* dl = m.get((size_t)B * 4);
+    std::vector<int> hm(2 * B);
+    for (int b = 0; b < B; ++b) {
+      hm[b] = Ns[b];
+      hm[B + b] = Ts[b];
+    }
+    HIPC(hipMemcpy(dc, cost, (size_t)B * cstride * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dmeta, hm.data(), hm.size() * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemset(df, 0xff, (size_t)B * n_max * 4));
+    HIPC(hipMemset(dp, 0xff, (size_t)B * pcap * 8));
+    HIPC(hipMemset(dl, 0, (size_t)B * 4));
+    if (!mwx::dtw_path((const float*)dc, dmeta, dmeta + B, B, n_max, t_max, cstride, n_max,
+                       (int*)df, pcap, (int*)dp, (int*)dl, nullptr))
+      return -4;
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(frames, df, (size_t)B * n_max * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(path, dp, (size_t)B * pcap * 8, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(path_len, dl, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return 0;
+  } catch (...) {
+    return -2;
+  }
+}
+
+extern "C" int mwx_test_dtw_keep(struct mwx_state* state, int on) {
+  if (!state) return -1;
+  const int prev = state->s.dtw_keep ? 1 : 0;
+  state->s.dtw_keep = on != 0;
+  if (!on) state->s.dtw_dump.clear();
+  return prev;
+}
+
+extern "C" int mwx_test_dtw_n_passes(struct mwx_state* state) {
+  return state ? (int)state->s.dtw_dump.size() : -1;
+}
+
+extern "C" int mwx_test_dtw_last(struct mwx_state* state, int pass, int* dims, int64_t* seek,
+                                 float* probs, long probs_cap, float* cost, long cost_cap,
+                                 int* frames, long frames_cap) {
+  if (!state || pass < 0 || pass >= (int)state->s.dtw_dump.size() || !dims) return -1;
+  const mwx::State::DtwDump& d = state->s.dtw_dump[pass];
+  dims[0] = d.N;
+  dims[1] = d.T;
+  dims[2] = d.A;
+  dims[3] = d.n_keys;
+  if (seek) *seek = d.seek;
+  if (probs) {
+    if (probs_cap < (long)d.probs.size()) return -1;
+    memcpy(probs, d.probs.data(), d.probs.size() * 4);
+  }
+  if (cost) {
+    if (cost_cap < (long)d.cost.size()) return -1;
+    memcpy(cost, d.cost.data(), d.cost.size() * 4);
+  }
+  if (frames) {
+    if (frames_cap < (long)d.frames.size()) return -1;
+    memcpy(frames, d.frames.data(), d.frames.size() * 4);
+  }
+  return 0;
+}
+
+namespace mwx {
+template <typename T>
+static int test_dtw_align_impl(Context& C, State& S, const int* tokens, int n, int pos0,
+                               int n_cols) {
+  mwx_full_params P = mwx_full_default_params(MWX_SAMPLING_GREEDY);
+  Driver<T> D(C, S, P);
+  typename Driver<T>::DtwClip x;
+  x.slot = 0;
+  x.tokens.assign(tokens, tokens + n);
+  x.pos0 = pos0;
+  x.n_rows = n - pos0;
+  x.n_cols = n_cols;
+  std::vector<typename Driver<T>::DtwClip> dc{x};
+  std::vector<State*> st{&S};
+  int64_t seek = 0;
+  const bool keep = S.dtw_keep;
+  S.dtw_keep = true;
+  S.dtw_dump.clear();
+  try {
+    D.dtw_pass(dc, st, &seek);
+  } catch (...) {
+    S.dtw_keep = keep;
+    throw;
+  }
+  S.dtw_keep = keep;
+  return 0;
+}
+}  // namespace mwx
+
+extern "C" int mwx_test_dtw_align(struct mwx_context* ctx, struct mwx_state* state,
+                                  const int* tokens, int n, int pos0, int n_cols) {
+  if (!ctx || !state || !tokens || !ctx->c.dtw || state->s.cross_cap < 1) return -1;
+  if (pos0 < 0 || n - pos0 < 2 || n - pos0 > mwx::DTW_MAX_ROWS || n > ctx->c.hp.n_text_ctx ||
+      n_cols < 1 || n_cols > ctx->c.hp.n_audio_ctx)
+    return -1;
+  if (!mwx::tokens_valid(tokens, n, ctx->c.hp.n_vocab)) return -1;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    if (ctx->c.wtype == mwx::GGML_BF16)
+      return mwx::test_dtw_align_impl<__bf16>(ctx->c, state->s, tokens, n, pos0, n_cols);
+    return mwx::test_dtw_align_impl<_Float16>(ctx->c, state->s, tokens, n, pos0, n_cols);
   } catch (...) {
     return -2;
   }

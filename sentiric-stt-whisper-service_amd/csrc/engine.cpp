@@ -161,6 +161,13 @@ struct Context {
   const float *dec_ln_w = nullptr, *dec_ln_b = nullptr;
   int space_id = -1;
   std::vector<int> nst_ids;  // suppress_nst token ids
+  // DTW token timestamps (mwx_context_params.dtw_*): the
+  // alignment heads (layer, head) in the caller's order (a = index), and on
+  // the device the (head, a) pairs grouped by decoder layer
+  bool dtw = false;
+  std::vector<std::pair<int, int>> dtw_heads;
+  int2* dtw_dev = nullptr;
+  std::vector<int> dtw_off, dtw_cnt;  // per decoder layer: first pair, pairs
 };
 
 struct Segment {
@@ -267,6 +274,21 @@ struct State {
   size_t energy_pin_n = 0;
   int cross_cap = 0;  // cross cache slots
   int row_cap = 0;    // self cache rows
+  // DTW token timestamps: the alignment pass's own self cache (dtw_rows rows:
+  // the decode rows' caches are never touched), the alignment heads'
+  // probabilities [slot][a][n][n_audio_ctx], cost matrices, frames and the
+  // per-clip (slot, N, T) words; with dtw_keep, every pass's results per clip
+  // on the host (mwx_test_dtw_last reads them; cleared by each mwx_full* call)
+  DBuf dtw_kself, dtw_vself, dtw_w, dtw_cost, dtw_frames, dtw_meta;
+  int dtw_rows = 0;
+  bool dtw_keep = false;
+  struct DtwDump {
+    int N = 0, T = 0, A = 0, n_keys = 0;
+    int64_t seek = 0;
+    std::vector<float> probs, cost;  // [A][N][n_keys], [N][T]
+    std::vector<int> frames;         // [N]
+  };
+  std::vector<DtwDump> dtw_dump;
   std::vector<Segment> result_all;
   int lang_id = 0;
   std::mt19937 rng0 = std::mt19937(0);  // decoders[0].rng persists per state
@@ -1170,6 +1192,12 @@ struct Driver {
     // cross-attention runs in groups of 8 virtual rows of one clip (one K/V
     // stream per group; every row's arithmetic is the single-row kernel's)
     bool prefill = false;
+    // DTW alignment pass (a prefill over its own self cache of self_rows
+    // rows): layers that own an alignment head also write those heads'
+    // probabilities of the rows at positions >= pos0
+    size_t self_rows = 0;  // rows of the cache at kself / vself (0: S.row_cap)
+    float* dtw_out = nullptr;
+    int dtw_pos0 = 0, dtw_rows_cap = 0;
   };
 
   // One pass of the decoder layer stack over a set of rows, in parts: the
@@ -1214,7 +1242,7 @@ struct Driver {
   void layer_pre(const LayerRows& rw, LayerRun& c, int l, hipStream_t s) {
     const int n = rw.n;
     const float kqs = powf(64.0f, -0.25f);
-    const size_t layer_self = (size_t)S.row_cap * H * Tctx * 64;
+    const size_t layer_self = (rw.self_rows ? rw.self_rows : (size_t)S.row_cap) * H * Tctx * 64;
     const DecLayerW& W = C.dec[l];
     _Float16* ks = rw.kself + l * layer_self;
     _Float16* vs = rw.vself + l * layer_self;
@@ -1285,6 +1313,16 @@ struct Driver {
       // cross-attention brackets: the two event nodes' own cost)
       PerfScope ps(S, "event_bracket", s);
       launch_perf_empty(s);
+    }
+    if (rw.dtw_out && C.dtw_cnt[l] > 0) {
+      PerfScope ps(S, "dtw_qk", s);
+      const size_t kbytes = l * layer_cross * (C.kv8 ? 1 : 2);
+      if (!align_probs(rw.Pq, c.k3, d, W.cq_b, 1.0f, kqs, (const uint8_t*)S.cross_k.p + kbytes,
+                       C.kv8 ? (const uint8_t*)S.cross_ks.p + l * layer_xs : nullptr, rw.xidx,
+                       rw.pos, rw.act, C.dtw_dev + C.dtw_off[l], C.dtw_cnt[l], hp.n_audio_ctx,
+                       hp.n_audio_ctx, n, H, rw.dtw_pos0, (int)C.dtw_heads.size(),
+                       rw.dtw_rows_cap, rw.dtw_out, s))
+        throw std::runtime_error("mwx: unsupported alignment shape");
     }
     PerfScope ps(S, rw.prefill ? "prefill_cross" : "dec_attn_cross", s);
     // the decoders of a beam / best-of group share their clip's cross K/V:
@@ -1380,7 +1418,13 @@ struct Driver {
     const int* tokens;       // prompt tokens
     int n;                   // positions to prefill (0 .. n-1)
   };
-  void prefill(const std::vector<PrefillRow>& prs) {
+  // dtw != nullptr: the DTW alignment pass (dtw_pass): its self cache, its
+  // alignment launches, not counted as prompt prefill
+  struct DtwRows {
+    int rows, pos0, rows_cap;
+    float* out;
+  };
+  void prefill(const std::vector<PrefillRow>& prs, const DtwRows* dtw = nullptr) {
     static const int vcap = std::max(64, getenv("MWX_PREFILL_ROWS")
                                              ? atoi(getenv("MWX_PREFILL_ROWS")) : 2048);
     int nmax = 0, nrows = 0;
@@ -1390,7 +1434,8 @@ struct Driver {
         ++nrows;
       }
     if (nrows == 0) return;
-    for (const auto& r : prs) S.n_prefill += std::max(0, r.n);
+    if (!dtw)
+      for (const auto& r : prs) S.n_prefill += std::max(0, r.n);
     // positions per chunk: every row with work gets the same span (x 8)
     static const int span_env = getenv("MWX_PREFILL_SPAN") ? atoi(getenv("MWX_PREFILL_SPAN")) : 0;
     const int span = span_env > 0 ? span_env : std::max(8, (vcap / nrows) / 8 * 8);
@@ -1417,6 +1462,14 @@ struct Driver {
     rw.vself = (_Float16*)S.vself.p;
     rw.prefill = true;
     rw.xgroup = q;
+    if (dtw) {
+      rw.kself = (_Float16*)S.dtw_kself.p;
+      rw.vself = (_Float16*)S.dtw_vself.p;
+      rw.self_rows = dtw->rows;
+      rw.dtw_out = dtw->out;
+      rw.dtw_pos0 = dtw->pos0;
+      rw.dtw_rows_cap = dtw->rows_cap;
+    }
     // host inputs of every chunk in one array (no reallocation while its
     // uploads are queued): the pass is queued without a synchronize, so the
     // host goes on to capture / launch the decode steps behind it
@@ -1481,6 +1534,88 @@ struct Driver {
       HIPC(hipEventDestroy(ev0));
       HIPC(hipEventDestroy(ev1));
     }
+  }
+
+  // DTW token timestamps of one window of the clips in `dc`:
+  // the teacher-forced alignment pass (a prefill with the alignment launches,
+  // over this pass's own self cache), the cost matrices and the DTW paths of
+  // all clips in one launch each, then the frames on the host (one
+  // synchronize). tokens = sot sequence + NOT + text tokens + EOT, N = the
+  // tokens from NOT on, T columns.
+  struct DtwClip {
+    int slot;                 // cross slot
+    std::vector<int> tokens;
+    int pos0, n_rows, n_cols;
+    std::vector<int> frames;  // out: [n_rows]
+  };
+  void dtw_pass(std::vector<DtwClip>& dc, const std::vector<State*>& clip_state, int64_t* seeks) {
+    const int nB = (int)dc.size();
+    if (nB == 0) return;
+    const int A = (int)C.dtw_heads.size(), n_keys = hp.n_audio_ctx;
+    int ncap = 0, tmax = 0;
+    for (const auto& c : dc) {
+      ncap = std::max(ncap, c.n_rows);
+      tmax = std::max(tmax, c.n_cols);
+    }
+    const size_t per = (size_t)L_dec * H * Tctx * 64 * 2;
+    if (S.dtw_rows < nB) {
+      S.dtw_kself.release();
+      S.dtw_vself.release();
+      S.dtw_kself.get(per * nB);
+      S.dtw_vself.get(per * nB);
+      S.dtw_rows = nB;
+    }
+    const size_t wclip = (size_t)A * ncap * n_keys;
+    float* w = (float*)S.dtw_w.get((size_t)S.cross_cap * wclip * 4);
+    const long cstride = (long)ncap * tmax;
+    float* cost = (float*)S.dtw_cost.get((size_t)nB * cstride * 4);
+    int* frames = (int*)S.dtw_frames.get((size_t)nB * ncap * 4);
+    int* meta = (int*)S.dtw_meta.get((size_t)3 * nB * 4);
+    std::vector<int> hm(3 * nB);
+    std::vector<PrefillRow> prs;
+    for (int i = 0; i < nB; ++i) {
+      hm[i] = dc[i].slot;
+      hm[nB + i] = dc[i].n_rows;
+      hm[2 * nB + i] = dc[i].n_cols;
+      prs.push_back({i, dc[i].slot, dc[i].tokens.data(), (int)dc[i].tokens.size()});
+    }
+    HIPC(hipMemcpyAsync(meta, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, st));
+    const DtwRows dr{S.dtw_rows, dc[0].pos0, ncap, w};
+    prefill(prs, &dr);
+    { PerfScope ps(S, "dtw_cost", st);
+      if (!dtw_cost(w, meta, meta + nB, meta + 2 * nB, nB, A, ncap, n_keys, tmax, cstride, cost, st))
+        throw std::runtime_error("mwx: unsupported DTW cost shape"); }
+    { PerfScope ps(S, "dtw_path", st);
+      if (!dtw_path(cost, meta + nB, meta + 2 * nB, nB, ncap, tmax, cstride, ncap, frames, 0,
+                    nullptr, nullptr, st))
+        throw std::runtime_error("mwx: unsupported DTW path shape"); }
+    std::vector<int> hf((size_t)nB * ncap);
+    HIPC(hipMemcpyAsync(hf.data(), frames, hf.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    bool kept = false;
+    for (int i = 0; i < nB; ++i) {
+      dc[i].frames.assign(hf.begin() + (size_t)i * ncap, hf.begin() + (size_t)i * ncap + dc[i].n_rows);
+      State& cs = *clip_state[i];
+      if (!cs.dtw_keep) continue;
+      cs.dtw_dump.emplace_back();
+      State::DtwDump& dd = cs.dtw_dump.back();
+      dd.N = dc[i].n_rows;
+      dd.T = dc[i].n_cols;
+      dd.A = A;
+      dd.n_keys = n_keys;
+      dd.seek = seeks[i];
+      dd.frames = dc[i].frames;
+      dd.cost.resize((size_t)dd.N * dd.T);
+      HIPC(hipMemcpyAsync(dd.cost.data(), cost + (size_t)i * cstride, dd.cost.size() * 4,
+                          hipMemcpyDeviceToHost, st));
+      dd.probs.resize((size_t)A * dd.N * n_keys);
+      for (int a = 0; a < A; ++a)
+        HIPC(hipMemcpyAsync(dd.probs.data() + (size_t)a * dd.N * n_keys,
+                            w + (size_t)dc[i].slot * wclip + (size_t)a * ncap * n_keys,
+                            (size_t)dd.N * n_keys * 4, hipMemcpyDeviceToHost, st));
+      kept = true;
+    }
+    if (kept) HIPC(hipStreamSynchronize(st));
   }
 
   // the decode-step rows (all R) and their buffers

@@ -252,47 +252,8 @@ void enc_attention(const _Float16* q, const _Float16* k, const _Float16* vt, T* 
 // ---------------------------------------------------------------------------
 constexpr int DEC_MAX_KEYS = 1536;
 
-__device__ __forceinline__ float block_max_256(float v, float* red) {
-  v = wave_max_dpp(v);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wid] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-__device__ __forceinline__ double block_sum_256d(double v, double* red) {
-  v = wave_sum_d_dpp(v);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wid] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-// q.k over 8 f16 elements with v_dot2_f32_f16 (q, k exact f16 values; f32
-// accumulation, pairs in index order): 4 instructions instead of 8 multiplies
-// and 8 adds. Used by every decode attention kernel, so all of them score a
-// row identically.
-__device__ __forceinline__ float dot8(const h2* q, f16x8 k) {
-  float d = __builtin_amdgcn_fdot2(q[0], __builtin_shufflevector(k, k, 0, 1), 0.0f, false);
-  d = __builtin_amdgcn_fdot2(q[1], __builtin_shufflevector(k, k, 2, 3), d, false);
-  d = __builtin_amdgcn_fdot2(q[2], __builtin_shufflevector(k, k, 4, 5), d, false);
-  d = __builtin_amdgcn_fdot2(q[3], __builtin_shufflevector(k, k, 6, 7), d, false);
-  return d;
-}
-
-// sum over the 8 lanes of an aligned lane group (DPP: xor 1, xor 2 within a
-// quad, then the mirrored quad); every lane of the group gets the same value.
-// update_dpp with bound_ctrl (all sources valid: the same values as mov_dpp)
-// lets each step compile to one v_add_f32_dpp instead of a v_mov_b32_dpp and
-// a v_add_f32
-__device__ __forceinline__ float dpp_sum8(float d) {
-  d += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(d), 0xB1, 0xF, 0xF, true));
-  d += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(d), 0x4E, 0xF, 0xF, true));
-  d += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(d), 0x141, 0xF, 0xF, true));
-  return d;
-}
+// (block_max_256, block_sum_256d, dot8, dpp_sum8, dequant_h8: kcommon.h, shared
+// with the alignment kernel of k_dtw.hip)
 
 // One workgroup per (row, head). Key/value rows are streamed in batches: 8
 // rows per 8-lane group (each lane 16 B of a 128-B row), 64 rows per wave,
@@ -688,15 +649,6 @@ __global__ __launch_bounds__(256) void dec_attn_kernel(
 #ifndef XATTN_VB
 #define XATTN_VB 2
 #endif
-__device__ __forceinline__ f16x8 dequant_h8(uint2 raw, uint32_t e) {
-  const float sc = e ? __uint_as_float(e << 23) : __uint_as_float(0x00400000u);
-  const h2 a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(raw.x, sc, false);
-  const h2 b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(raw.x, sc, true);
-  const h2 c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(raw.y, sc, false);
-  const h2 d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(raw.y, sc, true);
-  return f16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
-}
-
 // test hook (mwx_test_mx_widen): dequant_h8 itself on 8 codes per thread
 __global__ void mx_widen_test_kernel(const uint2* __restrict__ codes, const uint8_t* __restrict__ e8,
                                      int n8, f16x8* __restrict__ out) {

@@ -271,6 +271,34 @@ bool dec_cross_attention_grouped(const float* P, int KS, int pcols, const float*
                                  const uint8_t* vscale8 = nullptr,
                                  unsigned long long* span = nullptr);
 
+// DTW token timestamps (k_dtw.hip).
+constexpr int DTW_MAX_KEYS = 1536;  // encoder frames (n_audio_ctx)
+constexpr int DTW_MAX_ROWS = 256;   // alignment rows of a window (NOT + text tokens + EOT)
+// Alignment-head probabilities of the rows of a prefill chunk: for row r with
+// pos[r] >= pos0 and active[r], and every (head, a) pair of `heads`, the
+// softmax over the n_keys keys of slot kv_index[r] of q.k * scale, q =
+// f16((sum of the KS slabs of P + bias) * qscale), into
+// out[((kv_index[r] * A + a) * n_rows_cap + pos[r] - pos0) * n_keys ..]. kscale8
+// != nullptr: MX-fp8 cache (as dec_cross_attention_grouped). false: arguments
+// outside the kernel's limits (nothing launched).
+bool align_probs(const float* P, int KS, int pcols, const float* bias, float qscale, float scale,
+                 const void* kbase, const uint8_t* kscale8, const int* kv_index, const int* pos,
+                 const int* active, const int2* heads, int n_heads, int n_keys, int cap, int R, int H,
+                 int pos0, int A, int n_rows_cap, float* out, hipStream_t st);
+// cost[b][n][t] = -mean_a median7_t((w - mean_n) / std_n) over the first Ts[b]
+// columns and Ns[b] rows of clip b's probabilities (slot slot_of[b] of w, laid
+// out as align_probs writes it); clip b's matrix at cost + b * cost_stride,
+// rows compact.
+bool dtw_cost(const float* w, const int* slot_of, const int* Ns, const int* Ts, int n_clips, int A,
+              int n_rows_cap, int n_keys, int t_max, long cost_stride, float* cost, hipStream_t st);
+// The DTW path of every clip's cost matrix in one launch: frames[b *
+// n_rows_cap + n] = the first column of the path in row n. path (nullable):
+// the path's (row, column) pairs right-aligned in [path_cap] pairs per clip,
+// path_len[b] of them.
+bool dtw_path(const float* cost, const int* Ns, const int* Ts, int n_clips, int n_max, int t_max,
+              long cost_stride, int n_rows_cap, int* frames, int path_cap, int* path, int* path_len,
+              hipStream_t st);
+
 struct RowCtl {
   int active;        // row participates in this step
   int sample;        // logits of this step are processed (last prompt token or generated)

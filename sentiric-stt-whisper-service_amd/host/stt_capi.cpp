@@ -87,6 +87,7 @@ void* mwx_stt_new(const char* model_dir, const char* model_filename, int paralle
   s.vad_ms_min_duration = vad_ms_min;
   s.gpu_device = gpu_device;
   try {
+    settings_dtw_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -112,6 +113,7 @@ void* mwx_stt_new_batched(const char* model_dir, const char* model_filename,
   s.max_batch = max_batch;
   s.batch_window_us = batch_window_us;
   try {
+    settings_dtw_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -146,6 +148,7 @@ void* mwx_stt_new_ex(const char* model_dir, const char* model_filename, int para
   s.batch_window_us = batch_window_us;
   s.stream_buffer_samples = stream_buffer_samples;
   try {
+    settings_dtw_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -176,6 +179,7 @@ void* mwx_stt_new_vad(const char* model_dir, const char* model_filename, int par
   if (vad_model_filename) s.vad_model_filename = vad_model_filename;
   s.vad_threshold = vad_threshold;
   try {
+    settings_dtw_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -206,6 +210,7 @@ void* mwx_stt_new_vad_trim(const char* model_dir, const char* model_filename,
   s.vad_threshold = vad_threshold;
   s.vad_trim = vad_trim != 0;
   try {
+    settings_dtw_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());

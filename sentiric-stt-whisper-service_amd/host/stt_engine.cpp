@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 
 #include "text_filters.h"
 
@@ -118,12 +119,50 @@ std::string SpeakerClusterer::assign_or_add(const std::vector<float>& vec) {
   return id;
 }
 
+void settings_dtw_from_env(Settings& s) {
+  static const char* const kPresets[] = {"none", "n_top_most", "custom", "tiny.en", "tiny",
+                                         "base.en", "base", "small.en", "small", "medium.en",
+                                         "medium", "large-v1", "large-v2", "large-v3",
+                                         "large-v3-turbo"};  // enum mwx_alignment_heads_preset
+  if (const char* v = std::getenv("STT_WHISPER_SERVICE_DTW_TOKEN_TIMESTAMPS"))
+    s.dtw_token_timestamps = std::string(v) == "true" || std::string(v) == "1";
+  if (const char* v = std::getenv("STT_WHISPER_SERVICE_DTW_AHEADS_PRESET")) {
+    s.dtw_aheads_preset = -1;  // (an unknown name fails the context's check)
+    for (int i = 0; i < (int)(sizeof(kPresets) / sizeof(kPresets[0])); ++i)
+      if (std::string(v) == kPresets[i]) s.dtw_aheads_preset = i;
+  }
+  if (const char* v = std::getenv("STT_WHISPER_SERVICE_DTW_N_TOP")) s.dtw_n_top = std::atoi(v);
+  if (const char* v = std::getenv("STT_WHISPER_SERVICE_DTW_AHEADS")) {
+    s.dtw_aheads.clear();
+    const std::string str(v);
+    size_t p = 0;
+    while (p < str.size()) {
+      size_t q = str.find(',', p);
+      if (q == std::string::npos) q = str.size();
+      const std::string item = str.substr(p, q - p);
+      const size_t c = item.find(':');
+      if (c != std::string::npos)
+        s.dtw_aheads.emplace_back(std::atoi(item.substr(0, c).c_str()),
+                                  std::atoi(item.substr(c + 1).c_str()));
+      p = q + 1;
+    }
+  }
+}
+
 SttEngine::SttEngine(const Settings& settings) : settings_(settings) {
   const std::string path = settings_.model_dir + "/" + settings_.model_filename;
   mwx_context_params cp = mwx_context_default_params();
   cp.use_gpu = true;
   cp.flash_attn = settings_.flash_attn;
   cp.gpu_device = settings_.gpu_device;
+  std::vector<mwx_ahead> aheads;
+  for (const auto& a : settings_.dtw_aheads) aheads.push_back({a.first, a.second});
+  cp.dtw_token_timestamps = settings_.dtw_token_timestamps;
+  cp.dtw_aheads_preset = settings_.dtw_aheads_preset;
+  cp.dtw_n_top = settings_.dtw_n_top;
+  cp.dtw_aheads.n_heads = aheads.size();
+  cp.dtw_aheads.heads = aheads.empty() ? nullptr : aheads.data();
+  cp.dtw_mem_size = 0;
   ctx_ = mwx_init_from_file_with_params(path.c_str(), cp);
   if (!ctx_) throw std::runtime_error("Whisper model initialization failed");
   aux_state_ = mwx_init_state(ctx_);
@@ -399,6 +438,7 @@ std::vector<TranscriptionResult> SttEngine::collect(mwx_state* state, const std:
     const int64_t t1 = mwx_full_get_segment_t1_from_state(state, i);
     const bool turn = mwx_full_get_segment_speaker_turn_next_from_state(state, i);
     std::vector<TokenData> tokens;
+    std::vector<int64_t> t_dtw;
     double total_p = 0.0;
     int valid = 0;
     const int nt = mwx_full_n_tokens_from_state(state, i);
@@ -407,9 +447,19 @@ std::vector<TranscriptionResult> SttEngine::collect(mwx_state* state, const std:
       if (d.id >= eot) continue;
       const char* ts = mwx_token_to_str(ctx_, d.id);
       tokens.push_back({std::string(ts ? ts : ""), d.p, d.t0, d.t1});
+      t_dtw.push_back(d.t_dtw);
       total_p += d.p;
       ++valid;
     }
+    // dtw_token_timestamps: a kept token starts at its t_dtw and ends where
+    // the next kept token starts, the segment's last one at the segment's end
+    // (a token the context gave no t_dtw keeps its t0 / t1)
+    if (settings_.dtw_token_timestamps)
+      for (size_t k = 0; k < tokens.size(); ++k) {
+        if (t_dtw[k] < 0) continue;
+        tokens[k].t0 = t_dtw[k];
+        tokens[k].t1 = k + 1 < tokens.size() && t_dtw[k + 1] >= 0 ? t_dtw[k + 1] : t1;
+      }
     if (token_count) *token_count += valid;
     const float avg = valid > 0 ? static_cast<float>(total_p / valid) : 0.0f;
     if (avg < kMinAvgTokenProb && valid > 0) continue;

@@ -80,7 +80,27 @@ struct Settings {
   // state path.
   int max_batch = 1;
   int batch_window_us = 2000;
+  // Engine extension (whisper.h dtw_token_timestamps): the
+  // context computes mwx_token_data.t_dtw from the alignment heads'
+  // cross-attention, and TokenData.t0 / t1 (the service's words[].start / end)
+  // come from it instead of the token_timestamps heuristic: t0 = the token's
+  // t_dtw, t1 = the next kept token's t_dtw, the segment's t1 for its last
+  // token. dtw_aheads_preset is an enum mwx_alignment_heads_preset value;
+  // N_TOP_MOST reads dtw_n_top, CUSTOM dtw_aheads ((decoder layer, head)).
+  bool dtw_token_timestamps = false;
+  int dtw_aheads_preset = 0;
+  int dtw_n_top = -1;
+  std::vector<std::pair<int, int>> dtw_aheads;
 };
+
+// Reads the DTW settings from the environment, as the service reads its other
+// settings: STT_WHISPER_SERVICE_DTW_TOKEN_TIMESTAMPS (true / 1),
+// STT_WHISPER_SERVICE_DTW_AHEADS_PRESET (n_top_most, custom, tiny.en, tiny,
+// base.en, base, small.en, small, medium.en, medium, large-v1, large-v2,
+// large-v3, large-v3-turbo), STT_WHISPER_SERVICE_DTW_N_TOP and
+// STT_WHISPER_SERVICE_DTW_AHEADS ("layer:head,layer:head,..."). Unset
+// variables leave the fields as they are.
+void settings_dtw_from_env(Settings& s);
 
 // Owner of one mwx_vad_trimmed (vad_trim; defined in stt_engine.cpp).
 struct TrimmedAudio;

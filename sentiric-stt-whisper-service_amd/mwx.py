@@ -44,9 +44,28 @@ SAMPLING_GREEDY = 0
 SAMPLING_BEAM_SEARCH = 1
 
 
+class Ahead(C.Structure):
+    """mwx_ahead (whisper_ahead): one alignment head."""
+    _fields_ = [("n_text_layer", C.c_int), ("n_head", C.c_int)]
+
+
+class Aheads(C.Structure):
+    """mwx_aheads (whisper_aheads)."""
+    _fields_ = [("n_heads", C.c_size_t), ("heads", C.POINTER(Ahead))]
+
+
 class ContextParams(C.Structure):
     _fields_ = [("use_gpu", C.c_bool), ("flash_attn", C.c_bool), ("gpu_device", C.c_int),
-                ("compute", C.c_int)]
+                ("compute", C.c_int), ("dtw_token_timestamps", C.c_bool),
+                ("dtw_aheads_preset", C.c_int), ("dtw_n_top", C.c_int), ("dtw_aheads", Aheads),
+                ("dtw_mem_size", C.c_size_t)]
+
+
+# enum mwx_alignment_heads_preset (whisper_alignment_heads_preset)
+AHEADS_NONE, AHEADS_N_TOP_MOST, AHEADS_CUSTOM = 0, 1, 2
+(AHEADS_TINY_EN, AHEADS_TINY, AHEADS_BASE_EN, AHEADS_BASE, AHEADS_SMALL_EN, AHEADS_SMALL,
+ AHEADS_MEDIUM_EN, AHEADS_MEDIUM, AHEADS_LARGE_V1, AHEADS_LARGE_V2, AHEADS_LARGE_V3,
+ AHEADS_LARGE_V3_TURBO) = range(3, 15)
 
 
 COMPUTE_MODEL = 0
@@ -458,6 +477,7 @@ class Token:
     t0: int
     t1: int
     text: str
+    t_dtw: int = -1
 
 
 @dataclass
@@ -473,11 +493,24 @@ class Segment:
 class Context:
     """mwx_context + a pool of mwx_state objects."""
 
-    def __init__(self, model_path: str, device: int = 0, compute: int = COMPUTE_MODEL):
+    def __init__(self, model_path: str, device: int = 0, compute: int = COMPUTE_MODEL,
+                 dtw_preset: int = AHEADS_NONE, dtw_heads=None, dtw_n_top: int = -1):
+        """dtw_preset != AHEADS_NONE turns DTW token timestamps on
+        (mwx_context_params.dtw_token_timestamps): AHEADS_CUSTOM with dtw_heads
+        = [(layer, head), ...], AHEADS_N_TOP_MOST with dtw_n_top, or a model
+        preset."""
         L = lib()
         cp = L.mwx_context_default_params()
         cp.gpu_device = device
         cp.compute = compute
+        if dtw_preset != AHEADS_NONE:
+            cp.dtw_token_timestamps = True
+            cp.dtw_aheads_preset = dtw_preset
+            cp.dtw_n_top = dtw_n_top
+            if dtw_heads is not None:
+                arr = (Ahead * max(1, len(dtw_heads)))(*[Ahead(l, h) for l, h in dtw_heads])
+                cp.dtw_aheads.n_heads = len(dtw_heads)
+                cp.dtw_aheads.heads = arr
         self.ctx = L.mwx_init_from_file_with_params(model_path.encode(), cp)
         if not self.ctx:
             raise RuntimeError(f"mwx_init_from_file_with_params failed for {model_path}")
@@ -579,7 +612,7 @@ class Context:
                 td = L.mwx_full_get_token_data_from_state(s, i, j)
                 seg.tokens.append(Token(td.id, td.tid, td.p, td.plog, td.pt, td.ptsum, td.t0,
                                         td.t1, L.mwx_token_to_str(self.ctx, td.id).decode(
-                                            "utf-8", "replace")))
+                                            "utf-8", "replace"), td.t_dtw))
             out.append(seg)
         return out
 
@@ -849,6 +882,137 @@ class Context:
             raise RuntimeError(f"mwx_test_dec_attn failed ({rc})")
         return o, kc.view(np.float16), vc.view(np.float16)
 
+    def test_align_probs(self, P: np.ndarray, bias: np.ndarray, k: np.ndarray, *, heads, A: int,
+                         kv_index, pos, active, out: np.ndarray, pos0: int = 0,
+                         qscale: float = 1.0, scale: float = 1.0, kscale=None) -> np.ndarray:
+        """mwx_test_align_probs: P [KS][R][H*64] f32, bias [H*64], k
+        [slots][H][n_keys][64] float16 (or uint8 e4m3 codes with kscale
+        [slots][H][n_keys][2] uint8), heads [(head, a), ...], out
+        [slots][A][n_rows_cap][n_keys] f32 (a copy is filled and returned; rows
+        the launch does not write keep their values)."""
+        P = np.ascontiguousarray(P, dtype=np.float32)
+        bias = np.ascontiguousarray(bias, dtype=np.float32)
+        KS, R, D = P.shape
+        slots, H, n_keys, _ = k.shape
+        mx = kscale is not None
+        assert k.shape[3] == 64 and D == H * 64 and bias.shape == (D,)
+        assert k.dtype == (np.uint8 if mx else np.float16)
+        kc = np.ascontiguousarray(k)
+        ksc = np.ascontiguousarray(kscale, dtype=np.uint8) if mx else None
+        assert not mx or ksc.shape == (slots, H, n_keys, 2)
+        o = np.array(out, dtype=np.float32, order="C")
+        assert o.shape[0] == slots and o.shape[1] == A and o.shape[3] == n_keys
+        ip = C.POINTER(C.c_int)
+        hd = np.ascontiguousarray(heads, dtype=np.int32).reshape(-1, 2)
+        ints = [np.ascontiguousarray(a, dtype=np.int32) for a in (kv_index, pos, active)]
+        assert all(a.shape == (R,) for a in ints)
+        fn = lib().mwx_test_align_probs
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] + [C.c_int] * 7 + [ip, C.c_int, C.c_int, C.c_int,
+                                                      C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                      C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                                      ip, ip, ip, C.POINTER(C.c_float)]
+        rc = fn(self.ctx, int(mx), R, H, KS, n_keys, slots, len(hd), hd.ctypes.data_as(ip), A, pos0,
+                o.shape[2], fptr(P), fptr(bias), qscale, scale, kc.ctypes.data,
+                ksc.ctypes.data if mx else None, *[a.ctypes.data_as(ip) for a in ints], fptr(o))
+        if rc == -1:
+            raise ValueError("mwx_test_align_probs refused its arguments")
+        if rc != 0:
+            raise RuntimeError(f"mwx_test_align_probs failed ({rc})")
+        return o
+
+    def test_dtw_cost(self, w: np.ndarray, Ns, Ts) -> List[np.ndarray]:
+        """mwx_test_dtw_cost: w [B][A][n_rows_cap][n_keys] f32 probabilities;
+        returns clip b's cost matrix [Ns[b]][Ts[b]]."""
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        B, A, ncap, n_keys = w.shape
+        ns = np.ascontiguousarray(Ns, dtype=np.int32)
+        ts = np.ascontiguousarray(Ts, dtype=np.int32)
+        assert ns.shape == (B,) and ts.shape == (B,)
+        stride = ncap * int(ts.max())
+        cost = np.empty(B * stride, np.float32)
+        ip = C.POINTER(C.c_int)
+        fn = lib().mwx_test_dtw_cost
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] + [C.c_int] * 4 + [ip, ip, C.POINTER(C.c_float),
+                                                      C.POINTER(C.c_float)]
+        rc = fn(self.ctx, B, A, ncap, n_keys, ns.ctypes.data_as(ip), ts.ctypes.data_as(ip), fptr(w),
+                fptr(cost))
+        if rc != 0:
+            raise RuntimeError(f"mwx_test_dtw_cost failed ({rc})")
+        return [cost[b * stride:b * stride + ns[b] * ts[b]].reshape(ns[b], ts[b]).copy()
+                for b in range(B)]
+
+    def test_dtw_path(self, costs: Sequence[np.ndarray]):
+        """mwx_test_dtw_path: the DTW of B cost matrices [N_b][T_b] in one
+        launch. Returns [(frames [N_b], path [L_b][2] (row, column)), ...]."""
+        B = len(costs)
+        ns = np.array([c.shape[0] for c in costs], np.int32)
+        ts = np.array([c.shape[1] for c in costs], np.int32)
+        nm, tm = int(ns.max()), int(ts.max())
+        flat = np.zeros(B * nm * tm, np.float32)
+        for b, c in enumerate(costs):
+            flat[b * nm * tm:b * nm * tm + c.size] = np.ascontiguousarray(c, np.float32).ravel()
+        frames = np.empty((B, nm), np.int32)
+        path = np.empty((B, nm + tm, 2), np.int32)
+        plen = np.empty(B, np.int32)
+        ip = C.POINTER(C.c_int)
+        fn = lib().mwx_test_dtw_path
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, ip, ip, C.POINTER(C.c_float), ip, ip, ip]
+        rc = fn(self.ctx, B, ns.ctypes.data_as(ip), ts.ctypes.data_as(ip), fptr(flat),
+                frames.ctypes.data_as(ip), path.ctypes.data_as(ip), plen.ctypes.data_as(ip))
+        if rc != 0:
+            raise RuntimeError(f"mwx_test_dtw_path failed ({rc})")
+        return [(frames[b, :ns[b]].copy(), path[b, nm + tm - plen[b]:].copy()) for b in range(B)]
+
+    def dtw_keep(self, on: bool = True, state_index: int = 0) -> None:
+        """mwx_test_dtw_keep: the state keeps its DTW passes for dtw_passes()."""
+        fn = lib().mwx_test_dtw_keep
+        fn.argtypes = [C.c_void_p, C.c_int]
+        fn(self.state(state_index), int(on))
+
+    def test_dtw_align(self, tokens, pos0: int, n_cols: int, state_index: int = 0) -> dict:
+        """mwx_test_dtw_align: the alignment pass over `tokens` against the
+        cross K/V of the last test_encode on the state; returns the pass."""
+        tk = np.ascontiguousarray(tokens, dtype=np.int32)
+        fn = lib().mwx_test_dtw_align
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]
+        rc = fn(self.ctx, self.state(state_index), tk.ctypes.data_as(C.POINTER(C.c_int)), len(tk),
+                pos0, n_cols)
+        if rc != 0:
+            raise RuntimeError(f"mwx_test_dtw_align failed ({rc})")
+        return self.dtw_passes(state_index)[0]
+
+    def dtw_passes(self, state_index: int = 0) -> List[dict]:
+        """The DTW passes (one per window that emitted segments) of the
+        state's last call: dicts with seek, probs [A][N][n_audio_ctx], cost
+        [N][T], frames [N]."""
+        L = lib()
+        L.mwx_test_dtw_n_passes.argtypes = [C.c_void_p]
+        fn = L.mwx_test_dtw_last
+        fn.restype = C.c_int
+        ip = C.POINTER(C.c_int)
+        fn.argtypes = [C.c_void_p, C.c_int, ip, C.POINTER(C.c_int64), C.POINTER(C.c_float),
+                       C.c_long, C.POINTER(C.c_float), C.c_long, ip, C.c_long]
+        s = self.state(state_index)
+        out = []
+        for i in range(max(0, L.mwx_test_dtw_n_passes(s))):
+            dims = (C.c_int * 4)()
+            seek = C.c_int64()
+            if fn(s, i, dims, C.byref(seek), None, 0, None, 0, None, 0) != 0:
+                raise RuntimeError("mwx_test_dtw_last failed")
+            N, T, A, nk = list(dims)
+            probs = np.empty((A, N, nk), np.float32)
+            cost = np.empty((N, T), np.float32)
+            frames = np.empty(N, np.int32)
+            if fn(s, i, dims, C.byref(seek), fptr(probs), probs.size, fptr(cost), cost.size,
+                  frames.ctypes.data_as(ip), N) != 0:
+                raise RuntimeError("mwx_test_dtw_last failed")
+            out.append(dict(seek=seek.value, probs=probs, cost=cost, frames=frames))
+        return out
+
     def test_gemm_dec(self, a: np.ndarray, w: np.ndarray, *, bf16: bool, mode: int,
                       bias=None, res=None) -> np.ndarray:
         """mwx_test_gemm_dec: a [M][K], w [N][K] f32 (rounded to bf16 / f16 by the
@@ -923,8 +1087,9 @@ class Context:
         return self._hp
 
     @classmethod
-    def open(cls, model_path: str, device: int = 0, compute: int = COMPUTE_MODEL) -> "Context":
-        c = cls(model_path, device, compute)
+    def open(cls, model_path: str, device: int = 0, compute: int = COMPUTE_MODEL,
+             **dtw) -> "Context":
+        c = cls(model_path, device, compute, **dtw)
         c._hp = read_hparams(model_path)
         return c
 
