@@ -186,6 +186,14 @@ struct mwx_full_params {
   bool split_on_word;
   int max_tokens;
 
+  /* Audio context (INTEGRATION.md "Audio context"). 0 (the
+   * default; negative values count as 0): every window is encoded to
+   * n_audio_ctx frames. 1 .. n_audio_ctx: every window of every clip of the
+   * call is encoded from the first 2 * audio_ctx mel frames at its seek (a
+   * real frame past them counts as zero) to audio_ctx frames, and the decoder
+   * attends over audio_ctx keys; timestamp tokens stay 20-ms units and the
+   * window loop is unchanged. audio_ctx == n_audio_ctx is bit-identical to 0;
+   * more than n_audio_ctx: the call returns -5. See also audio_ctx_fit. */
   int audio_ctx;
   bool tdrz_enable;
 
@@ -224,6 +232,15 @@ struct mwx_full_params {
    * window, so each window costs the same fixed number of decode steps and a
    * long clip runs window after window. */
   int bench_fixed_steps;
+
+  /* Engine extension (appended field), off by default: every window of every
+   * clip gets its own audio context, fitted to the audio left in the clip:
+   * mwx_audio_ctx_for(ctx, n_samples, seek, audio_ctx, true), with audio_ctx
+   * (> 0) as the floor. A clip's result is bit-identical to the clip run alone
+   * with audio_ctx set to that value, whatever else is in the batch. The
+   * effect of a short context on recognition quality is unmeasured (no real
+   * checkpoint has been run with it): opt-in. */
+  bool audio_ctx_fit;
 };
 
 /* --- lifecycle --------------------------------------------------------- */
@@ -507,6 +524,14 @@ mwx_token mwx_token_lang(struct mwx_context* ctx, int lang_id);
 int mwx_n_vocab(struct mwx_context* ctx);
 int mwx_n_text_ctx(struct mwx_context* ctx);
 int mwx_n_audio_ctx(struct mwx_context* ctx);
+/* The audio context of the window at `seek` (mel frames, 10 ms) of a clip of
+ * n_samples samples under mwx_full_params.audio_ctx / audio_ctx_fit (a host
+ * function). With N = n_audio_ctx: fit off: audio_ctx > 0 ? audio_ctx : N. fit on, rem =
+ * max(0, n_len_org - seek) real mel frames left and floor = audio_ctx > 0 ?
+ * audio_ctx : 64: min(N, max(floor, 64 * ceil((ceil(rem / 2) + 32) / 64))),
+ * i.e. 0.64 s of trailing context, rounded up to the attention key tile.
+ * ctx may be NULL: N = 1500, every Whisper model's. -1: audio_ctx > N. */
+int mwx_audio_ctx_for(struct mwx_context* ctx, int n_samples, int seek, int audio_ctx, bool fit);
 int mwx_n_mels(struct mwx_context* ctx);
 int mwx_is_multilingual(struct mwx_context* ctx);
 int mwx_model_wtype(struct mwx_context* ctx); /* 1 = f16, 30 = bf16 */

@@ -26,6 +26,13 @@ int mwx_test_mel(struct mwx_context* ctx, struct mwx_state* state, const float* 
 int mwx_test_encode(struct mwx_context* ctx, struct mwx_state* state, const float* pcm, int n,
                     int seek, float* enc_out, float* k_out, float* v_out);
 
+/* mwx_test_encode at an audio context of audio_ctx = K frames (1 ..
+ * n_audio_ctx; else -5; mwx_full_params.audio_ctx): enc_out [K][n_audio_state],
+ * k_out / v_out [n_text_layer][K][n_audio_state]. The cross K/V and the key
+ * count K stay resident in `state` for mwx_test_decode* / mwx_test_dtw_align. */
+int mwx_test_encode_ctx(struct mwx_context* ctx, struct mwx_state* state, const float* pcm, int n,
+                        int seek, int audio_ctx, float* enc_out, float* k_out, float* v_out);
+
 /* Teacher-forced decoder run against the cross K/V left by mwx_test_encode:
  * token i at position i, logits_out [n][n_vocab] (raw logits). */
 /* The encoder of one clip window with its intermediates copied out: x_out

@@ -377,6 +377,17 @@ static bool stream_prio_has(const char* what) {
   return v == "both" || v.find(what) != std::string::npos;
 }
 
+// The audio context of a window (mwx.h: mwx_audio_ctx_for; DESIGN.md D9):
+// n_len_org real mel frames in the clip, the window at frame `seek`.
+static int audio_ctx_rule(int N, int n_len_org, int seek, int audio_ctx, bool fit) {
+  const int a = std::max(0, audio_ctx);
+  if (!fit) return a > 0 ? std::min(a, N) : N;
+  const int rem = std::max(0, n_len_org - seek);
+  const int floor_ctx = a > 0 ? a : 64;
+  const int want = 64 * (((rem + 1) / 2 + 32 + 63) / 64);
+  return std::min(N, std::max(floor_ctx, want));
+}
+
 template <typename T>
 static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
                     const void* const* pcm, const int* n_samples, int n_clips,
@@ -391,10 +402,7 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
     states[c]->s.dtw_dump.clear();
   }
   if (P.audio_ctx > hp.n_audio_ctx) return -5;
-  if (P.audio_ctx > 0 && P.audio_ctx != hp.n_audio_ctx) {
-    MWX_LOG_ERROR("mwx: audio_ctx < n_audio_ctx is not supported\n");
-    return -5;
-  }
+  if (P.audio_ctx < 0) P.audio_ctx = 0;
   const bool beam = P.strategy == MWX_SAMPLING_BEAM_SEARCH;
   if (beam && P.beam_search.beam_size < 1) return -4;
   std::vector<ClipRun> clips(n_clips);
@@ -487,16 +495,27 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
   }
   Driver<T> D(C, S, P);
   D.ensure_cross(n_clips);
+  D.reset_xkeys();
+  // the audio context of clip c's window at `seek` (DESIGN.md D9)
+  const bool actx_on = P.audio_ctx > 0 || P.audio_ctx_fit;
+  auto window_ctx = [&](int c, int seek) {
+    return audio_ctx_rule(hp.n_audio_ctx, clips[c].n_len_org, seek, P.audio_ctx, P.audio_ctx_fit);
+  };
   // ---------------- language detection ----------------
   const bool detect = P.language == nullptr || strlen(P.language) == 0 ||
                       strcmp(P.language, "auto") == 0 || P.detect_language;
-  auto encode_clips = [&](const std::vector<int>& which, const std::vector<int>& seeks) -> int {
+  // live: the clips whose cross slots the decode after this encode reads
+  auto encode_clips = [&](const std::vector<int>& which, const std::vector<int>& seeks,
+                          const std::vector<int>& live) -> int {
     if (which.empty()) return 0;
     if (aborted(P)) return -6;
-    std::vector<int> nlen, slots;
-    for (int c : which) {
+    D.live_slots = live;  // (slot = clip index)
+    std::vector<int> nlen, slots, nctx;
+    for (size_t i = 0; i < which.size(); ++i) {
+      const int c = which[i];
       nlen.push_back(clips[c].n_len);
       slots.push_back(c);
+      if (actx_on) nctx.push_back(window_ctx(c, seeks[i]));
     }
     if (stream_prio_has("enc_low")) {
       // the encoder on the state's low-priority stream, between two events
@@ -510,12 +529,12 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
       HIPC(hipEventRecord(S.ev_e0, st));
       HIPC(hipStreamWaitEvent(S.estream, S.ev_e0, 0));
       D.st = S.estream;
-      D.encode(which, seeks, nlen, slots, mel_stride);
+      D.encode(which, seeks, nlen, slots, mel_stride, nctx);
       D.st = st;
       HIPC(hipEventRecord(S.ev_e1, S.estream));
       HIPC(hipStreamWaitEvent(st, S.ev_e1, 0));
     } else {
-      D.encode(which, seeks, nlen, slots, mel_stride);
+      D.encode(which, seeks, nlen, slots, mel_stride, nctx);
     }
     for (size_t i = 0; i < which.size(); ++i) clips[which[i]].enc_seek = seeks[i];
     return 0;
@@ -528,7 +547,7 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
       which.push_back(c);
       seeks.push_back(0);
     }
-    if (int rc = encode_clips(which, seeks)) return rc;
+    if (int rc = encode_clips(which, seeks, which)) return rc;
     const int R = (int)which.size();
     if (R > 0) {
       D.ensure_rows(R);
@@ -642,7 +661,8 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
           which.push_back(c);
           seeks.push_back(clips[c].seek);
         }
-      if (int rc = encode_clips(which, seeks)) return rc;
+      D.live_slots = act;  // (also when nothing is encoded: the detection's encode is reused)
+      if (int rc = encode_clips(which, seeks, act)) return rc;
     }
     for (int c : act) {
       ClipRun& cr = clips[c];
@@ -1390,7 +1410,7 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
         x.n_rows = (int)x.tokens.size() - x.pos0;
         if (x.n_rows <= 2 || (int)x.tokens.size() > D.Tctx || x.n_rows > DTW_MAX_ROWS) continue;
         const int rem = (int)(clips[c].seek_end - dtw_seek[c]);
-        x.n_cols = std::max(1, std::min(P.audio_ctx > 0 ? P.audio_ctx : hp.n_audio_ctx, (rem + 1) / 2));
+        x.n_cols = std::max(1, std::min(D.slot_keys(c), (rem + 1) / 2));
         dc.push_back(std::move(x));
         dst.push_back(&cs);
         dsk.push_back(dtw_seek[c]);
@@ -1626,7 +1646,7 @@ void mwx_free_state(struct mwx_state* state) {
                        &S.pf_in, &S.pf_x, &S.pf_h, &S.pf_o, &S.pf_ff, &S.pf_pqkv,
                        &S.pf_pres, &S.pf_pq, &S.perf_span,
                        &S.dtw_kself, &S.dtw_vself, &S.dtw_w, &S.dtw_cost, &S.dtw_frames,
-                       &S.dtw_meta};
+                       &S.dtw_meta, &S.xkeys};
   for (auto* b : bufs) b->release();
   if (S.pin) (void)hipHostFree(S.pin);
   S.pin = nullptr;
@@ -1680,6 +1700,7 @@ struct mwx_full_params mwx_full_default_params(int strategy) {
   p.split_on_word = false;
   p.max_tokens = 0;
   p.audio_ctx = 0;
+  p.audio_ctx_fit = false;
   p.tdrz_enable = false;
   p.initial_prompt = nullptr;
   p.prompt_tokens = nullptr;
@@ -2071,6 +2092,13 @@ mwx_token mwx_token_lang(struct mwx_context* ctx, int lang_id) {
 int mwx_n_vocab(struct mwx_context* ctx) { return ctx->c.hp.n_vocab; }
 int mwx_n_text_ctx(struct mwx_context* ctx) { return ctx->c.hp.n_text_ctx; }
 int mwx_n_audio_ctx(struct mwx_context* ctx) { return ctx->c.hp.n_audio_ctx; }
+int mwx_audio_ctx_for(struct mwx_context* ctx, int n_samples, int seek, int audio_ctx, bool fit) {
+  const int N = ctx ? ctx->c.hp.n_audio_ctx : 1500;
+  if (audio_ctx > N) return -1;
+  const int n = std::max(0, n_samples);
+  const int n_len_org = n > 0 ? 1 + (n + 200 - 400) / MWX_HOP_LENGTH : 0;
+  return mwx::audio_ctx_rule(N, n_len_org, seek, audio_ctx, fit);
+}
 int mwx_n_mels(struct mwx_context* ctx) { return ctx->c.hp.n_mels; }
 int mwx_is_multilingual(struct mwx_context* ctx) { return ctx->c.vocab.is_multilingual() ? 1 : 0; }
 int mwx_model_wtype(struct mwx_context* ctx) { return ctx->c.wtype; }
@@ -2190,19 +2218,25 @@ static void to_f32_host(const void* dev, size_t n, float* out, hipStream_t st) {
 
 template <typename T>
 static int test_encode_impl(Context& C, State& S, const float* pcm, int n, int seek, float* enc_out,
-                            float* k_out, float* v_out) {
+                            float* k_out, float* v_out, int audio_ctx = 0) {
   long stride = 0;
   const int n_len = test_mel_impl(C, S, pcm, n, &stride);
   mwx_full_params P = mwx_full_default_params(MWX_SAMPLING_GREEDY);
   Driver<T> D(C, S, P);
   D.ensure_cross(1);
-  D.encode({0}, {seek}, {n_len}, {0}, stride);
-  const int L = C.hp.n_audio_ctx, d = C.hp.n_audio_state, H = C.hp.n_audio_head;
+  // Lcap: (time) rows of a cache slot; L: the rows this encode produced
+  const int Lcap = C.hp.n_audio_ctx, d = C.hp.n_audio_state, H = C.hp.n_audio_head;
+  const int L = audio_ctx > 0 ? audio_ctx : Lcap;
+  if (audio_ctx > 0)
+    D.encode({0}, {seek}, {n_len}, {0}, stride, {audio_ctx});
+  else
+    D.encode({0}, {seek}, {n_len}, {0}, stride);
+  // (the rows of one clip are the first rows of the buffer at any row count)
   if (enc_out) to_f32_host<T>(S.enc.p, (size_t)L * d, enc_out, S.stream);
   for (int kv = 0; kv < 2; ++kv) {
     float* dst = kv == 0 ? k_out : v_out;
     if (!dst) continue;
-    const size_t per_layer = (size_t)S.cross_cap * H * L * 64;
+    const size_t per_layer = (size_t)S.cross_cap * H * Lcap * 64;
     const size_t n_el = (size_t)C.hp.n_text_layer * per_layer;
     std::vector<float> f(n_el);
     if (S.cross_kv8) {  // MX-fp8 cache: codes x 2^(scale - 127)
@@ -2225,7 +2259,7 @@ static int test_encode_impl(Context& C, State& S, const float* pcm, int n, int s
         for (int t = 0; t < L; ++t)
           for (int e = 0; e < 64; ++e)
             dst[((size_t)l * L + t) * d + hh * 64 + e] =
-                f[(size_t)l * per_layer + (((size_t)hh * L + t) * 64) + e];
+                f[(size_t)l * per_layer + (((size_t)hh * Lcap + t) * 64) + e];
   }
   return 0;
 }
@@ -2250,6 +2284,7 @@ static int test_decode_impl(Context& C, State& S, const int* tokens, int n, floa
                             bool last_only = false) {
   mwx_full_params P = mwx_full_default_params(MWX_SAMPLING_GREEDY);
   Driver<T> D(C, S, P);
+  D.live_slots = {0};
   D.ensure_rows(1);
   D.build_static_mask();
   const int V = C.hp.n_vocab;
@@ -2278,6 +2313,7 @@ static int test_decode_prefill_impl(Context& C, State& S, const int* tokens, int
                                     float* logits_last) {
   mwx_full_params P = mwx_full_default_params(MWX_SAMPLING_GREEDY);
   Driver<T> D(C, S, P);
+  D.live_slots = {0};
   D.ensure_rows(1);
   D.build_static_mask();
   if (n > 1) {
@@ -2369,6 +2405,22 @@ int mwx_test_encode(struct mwx_context* ctx, struct mwx_state* state, const floa
     if (ctx->c.wtype == mwx::GGML_BF16)
       return mwx::test_encode_impl<__bf16>(ctx->c, state->s, pcm, n, seek, enc_out, k_out, v_out);
     return mwx::test_encode_impl<_Float16>(ctx->c, state->s, pcm, n, seek, enc_out, k_out, v_out);
+  } catch (...) {
+    return -1;
+  }
+}
+
+int mwx_test_encode_ctx(struct mwx_context* ctx, struct mwx_state* state, const float* pcm, int n,
+                        int seek, int audio_ctx, float* enc_out, float* k_out, float* v_out) {
+  if (!ctx || !state || !pcm || n <= 0) return -1;
+  if (audio_ctx < 1 || audio_ctx > ctx->c.hp.n_audio_ctx) return -5;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    if (ctx->c.wtype == mwx::GGML_BF16)
+      return mwx::test_encode_impl<__bf16>(ctx->c, state->s, pcm, n, seek, enc_out, k_out, v_out,
+                                           audio_ctx);
+    return mwx::test_encode_impl<_Float16>(ctx->c, state->s, pcm, n, seek, enc_out, k_out, v_out,
+                                           audio_ctx);
   } catch (...) {
     return -1;
   }
@@ -3069,6 +3121,7 @@ static int test_dtw_align_impl(Context& C, State& S, const int* tokens, int n, i
                                int n_cols) {
   mwx_full_params P = mwx_full_default_params(MWX_SAMPLING_GREEDY);
   Driver<T> D(C, S, P);
+  D.live_slots = {0};
   typename Driver<T>::DtwClip x;
   x.slot = 0;
   x.tokens.assign(tokens, tokens + n);

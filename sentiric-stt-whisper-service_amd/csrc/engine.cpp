@@ -190,6 +190,15 @@ struct State {
   DBuf pcm, mel, melmax, melT, h1p, x, h, q, k, vt, o, ff, enc, cross_k, cross_v;
   DBuf cross_ks, cross_vs;  // MX-fp8 cross cache: E8M0 scales (kv8)
   bool cross_kv8 = false;   // layout of cross_k / cross_v
+  // audio context: the key count of every cross slot, on the
+  // device (written by the encode path in stream order, read by the
+  // cross-attention kernels when any slot is shorter than n_audio_ctx) and its
+  // host mirror
+  DBuf xkeys;
+  std::vector<int> xkeys_h;
+  // the padded encoder buffers' layout: rows per clip of the last encode, and
+  // the slots whose zero rows are in place for it
+  int enc_rows = 0, enc_slots_zeroed = 0;
   DBuf energy, pcm16;
   DBuf meld, melpart;  // batched log-mel: per-clip descriptors, partial maxima
   // incremental log-mel (streaming re-transcription of a growing buffer):
@@ -830,7 +839,7 @@ struct Driver {
   hipStream_t st;
   const mwx_full_params& P;
   const Hparams& hp;
-  int d, H, L_enc, L_dec, V, Tctx, Lp;
+  int d, H, L_enc, L_dec, V, Tctx;
   LogitsConst LC;
   // run-ahead: the step's lp_pick runs inside the advance kernel (pick_in())
   bool pick_in_advance = false;
@@ -868,7 +877,6 @@ struct Driver {
     L_dec = hp.n_text_layer;
     V = hp.n_vocab;
     Tctx = hp.n_text_ctx;
-    Lp = (hp.n_audio_ctx + 7) & ~7;
     LC.n_vocab = V;
     LC.eot = C.vocab.token_eot;
     LC.beg = C.vocab.token_beg;
@@ -917,21 +925,67 @@ struct Driver {
   }
 
   // ---------------- encoder: nb windows -> cross K/V slots ----------------
+  // audio context: the key count of every cross slot. Any slot
+  // shorter than n_audio_ctx: the cross-attention readers take their key count
+  // from the device array; otherwise today's launches, which never read it.
+  // live_slots: the cross slots the current decode reads (empty: all)
+  std::vector<int> live_slots;
+  bool xvar() const {
+    if (live_slots.empty()) {
+      for (int v : S.xkeys_h)
+        if (v != hp.n_audio_ctx) return true;
+      return false;
+    }
+    for (int s : live_slots)
+      if (slot_keys(s) != hp.n_audio_ctx) return true;
+    return false;
+  }
+  const int* xkeys() const { return xvar() ? (const int*)S.xkeys.p : nullptr; }
+  int slot_keys(int slot) const {
+    return slot >= 0 && slot < (int)S.xkeys_h.size() ? S.xkeys_h[slot] : hp.n_audio_ctx;
+  }
+  void reset_xkeys() { S.xkeys_h.assign(std::max(1, S.cross_cap), hp.n_audio_ctx); }
+
+  // nctx_of_slot (empty: n_audio_ctx everywhere): the frames window i is
+  // encoded to. The launch shapes follow the largest (rows per clip Lc, a
+  // multiple of 8); a window's rows past its own count are computed from the
+  // zero frames past 2 n_ctx and stored, and nothing valid reads them, so a
+  // window's result does not depend on its batch mates.
   void encode(const std::vector<int>& clip_of_slot, const std::vector<int>& seek_of_slot,
               const std::vector<int>& nlen_of_slot, const std::vector<int>& cross_slot,
-              long mel_clip_stride) {
+              long mel_clip_stride, const std::vector<int>& nctx_of_slot = {}) {
     const int nb = (int)clip_of_slot.size();
-    const int Lc = hp.n_audio_ctx, T2 = 2 * Lc, cp = C.cpad;
+    const int N = hp.n_audio_ctx;
+    int nmax = 0;
+    bool var = false;
+    for (int i = 0; i < nb; ++i) {
+      const int v = i < (int)nctx_of_slot.size() ? nctx_of_slot[i] : N;
+      if (v < 1 || v > N) throw std::runtime_error("mwx: audio context out of range");
+      var |= v != N;
+      nmax = std::max(nmax, v);
+    }
+    const int Lc = var ? std::min(N, (nmax + 7) & ~7) : N, T2 = 2 * Lc, cp = C.cpad;
+    const int Lp = (Lc + 7) & ~7;
     const int M = nb * Lc;
-    int* ib = (int*)S.ibuf.get(sizeof(int) * 4 * 4096);
-    std::vector<int> hb(4 * 4096, 0);
+    if (nb > 4096) throw std::runtime_error("mwx: too many windows in one encode");
+    int* ib = (int*)S.ibuf.get(sizeof(int) * 5 * 4096);
+    std::vector<int> hb(5 * 4096, 0);
+    if ((int)S.xkeys_h.size() < S.cross_cap) S.xkeys_h.resize(S.cross_cap, N);
     for (int i = 0; i < nb; ++i) {
       hb[i] = clip_of_slot[i];
       hb[4096 + i] = seek_of_slot[i];
       hb[2 * 4096 + i] = nlen_of_slot[i];
       hb[3 * 4096 + i] = cross_slot[i];
+      hb[4 * 4096 + i] = var ? nctx_of_slot[i] : N;
+      S.xkeys_h.at(cross_slot[i]) = hb[4 * 4096 + i];
     }
     HIPC(hipMemcpyAsync(ib, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, st));
+    const int* lens = var ? ib + 4 * 4096 : nullptr;
+    bool any_short = false;  // (any slot, live or not: the readers index the whole array)
+    for (int v : S.xkeys_h) any_short |= v != N;
+    if (any_short)  // (stream order: after the last reader of the previous counts)
+      HIPC(hipMemcpyAsync(S.xkeys.get(S.xkeys_h.size() * 4), S.xkeys_h.data(),
+                          S.xkeys_h.size() * 4, hipMemcpyHostToDevice, st));
     _Float16* melT = (_Float16*)S.melT.get((size_t)nb * (T2 + 2) * cp * 2, true);
     _Float16* h1p = (_Float16*)S.h1p.get((size_t)nb * (T2 + 2) * d * 2, true);
     float* x = (float*)S.x.get((size_t)M * d * 4);
@@ -939,12 +993,30 @@ struct Driver {
     _Float16* q = (_Float16*)S.q.get((size_t)M * d * 2);
     _Float16* k = (_Float16*)S.k.get((size_t)M * d * 2);
     _Float16* vt = (_Float16*)S.vt.get((size_t)nb * H * 64 * Lp * 2, true);
+    // the zero rows / columns of the padded buffers sit where the last
+    // encode's row count put them: at another count (or for slots this count
+    // has not used yet) the pad rows 0 and T2 + 1 of every slot and the V^T
+    // columns Lc .. Lp are cleared; everything else is overwritten below
+    if (S.enc_rows == 0) S.enc_slots_zeroed = nb;  // (fresh, zero-filled buffers)
+    else if (S.enc_rows != Lc) S.enc_slots_zeroed = 0;
+    if (nb > S.enc_slots_zeroed) {
+      const size_t pm = (size_t)(T2 + 2) * cp * 2, ph = (size_t)(T2 + 2) * d * 2;
+      HIPC(hipMemset2DAsync(melT, pm, 0, (size_t)cp * 2, nb, st));
+      HIPC(hipMemset2DAsync(melT + (size_t)(T2 + 1) * cp, pm, 0, (size_t)cp * 2, nb, st));
+      HIPC(hipMemset2DAsync(h1p, ph, 0, (size_t)d * 2, nb, st));
+      HIPC(hipMemset2DAsync(h1p + (size_t)(T2 + 1) * d, ph, 0, (size_t)d * 2, nb, st));
+      if (Lp > Lc)
+        HIPC(hipMemset2DAsync(vt + Lc, (size_t)Lp * 2, 0, (size_t)(Lp - Lc) * 2,
+                              (size_t)nb * H * 64, st));
+      S.enc_slots_zeroed = nb;
+    }
+    S.enc_rows = Lc;
     T* o = (T*)S.o.get((size_t)M * d * sizeof(T));
     T* ff = (T*)S.ff.get((size_t)M * 4 * d * sizeof(T));
     T* enc = (T*)S.enc.get((size_t)M * d * sizeof(T));
     { PerfScope ps(S, "mel", st);
     launch_mel_window((const float*)S.mel.p, mel_clip_stride, ib, ib + 4096, ib + 2 * 4096,
-                      hp.n_mels, T2, cp, melT, nb, st); }
+                      hp.n_mels, T2, cp, melT, nb, st, lens); }
     EpiParams e;
     // conv1 (k3 s1 p1) as a GEMM over overlapping rows of the padded window
     e.bias = C.conv1_b;
@@ -1002,7 +1074,7 @@ struct Driver {
       mgemm(EPI_ENC_QKV, h, d, W.qkv_x, W.qkv_w, 3 * d, e); }
       if (dump) dump_copy(dump->a[0] + l * md, h, md * 2);
       { PerfScope ps(S, "enc_attn", st);
-      enc_attention<T>(q, k, vt, o, nb, H, Lc, kq_scale, st); }
+      enc_attention<T>(q, k, vt, o, nb, H, Lc, kq_scale, st, lens); }
       if (dump) dump_copy(dump->a[1] + l * md, o, md * 2);
       e = EpiParams();
       e.bias = W.o_b;
@@ -1046,6 +1118,7 @@ struct Driver {
       e.vs8 = (uint8_t*)S.cross_vs.p;
     }
     e.L = Lc;
+    e.lcap = N;  // (the cache keeps n_audio_ctx rows per slot at any Lc)
     e.H = H;
     e.d = d;
     e.ncap = S.cross_cap;
@@ -1074,6 +1147,8 @@ struct Driver {
       S.cross_cap = n_slots;
       S.cross_kv8 = C.kv8;
     }
+    S.xkeys.get((size_t)S.cross_cap * 4);
+    if ((int)S.xkeys_h.size() != S.cross_cap) S.xkeys_h.resize(S.cross_cap, hp.n_audio_ctx);
   }
 
   void ensure_rows(int R) {
@@ -1307,6 +1382,8 @@ struct Driver {
     const size_t layer_cross = (size_t)S.cross_cap * H * hp.n_audio_ctx * 64;  // elements
     const size_t layer_xs = (size_t)S.cross_cap * H * hp.n_audio_ctx * 2;      // kv8 scales
     const DecLayerW& W = C.dec[l];
+    // (nullptr unless a slot holds fewer than n_audio_ctx keys: today's launches)
+    const int* xk = xkeys();
     if (!rw.prefill && perf_on(S, "event_bracket")) {
       // calibration: the same event pair around an empty kernel at the same
       // point of the chain (bench.py subtracts its average from the
@@ -1321,7 +1398,7 @@ struct Driver {
                        C.kv8 ? (const uint8_t*)S.cross_ks.p + l * layer_xs : nullptr, rw.xidx,
                        rw.pos, rw.act, C.dtw_dev + C.dtw_off[l], C.dtw_cnt[l], hp.n_audio_ctx,
                        hp.n_audio_ctx, n, H, rw.dtw_pos0, (int)C.dtw_heads.size(),
-                       rw.dtw_rows_cap, rw.dtw_out, s))
+                       rw.dtw_rows_cap, rw.dtw_out, s, xk))
         throw std::runtime_error("mwx: unsupported alignment shape");
     }
     PerfScope ps(S, rw.prefill ? "prefill_cross" : "dec_attn_cross", s);
@@ -1336,19 +1413,20 @@ struct Driver {
               (const uint8_t*)S.cross_v.p + l * layer_cross, rw.xidx, rw.act, hp.n_audio_ctx,
               hp.n_audio_ctx, rw.od, n, H, kqs, nq, s,
               (const uint8_t*)S.cross_ks.p + l * layer_xs,
-              (const uint8_t*)S.cross_vs.p + l * layer_xs, sp))
+              (const uint8_t*)S.cross_vs.p + l * layer_xs, sp, xk))
         throw std::runtime_error("mwx: unsupported fp8 cross-attention group");
     } else if (nq < 2 ||
                !dec_cross_attention_grouped<T>(rw.Pq, c.k3, d, W.cq_b,
                                                (const _Float16*)S.cross_k.p + l * layer_cross,
                                                (const _Float16*)S.cross_v.p + l * layer_cross,
                                                rw.xidx, rw.act, hp.n_audio_ctx, hp.n_audio_ctx,
-                                               rw.od, n, H, kqs, nq, s, nullptr, nullptr, sp)) {
+                                               rw.od, n, H, kqs, nq, s, nullptr, nullptr, sp,
+                                               xk)) {
       dec_attention<T>(rw.Pq, c.k3, d, W.cq_b, 1.0f, 1.0f,
                        (_Float16*)S.cross_k.p + l * layer_cross,
                        (_Float16*)S.cross_v.p + l * layer_cross, rw.xidx, rw.pos, rw.act,
                        hp.n_audio_ctx, hp.n_audio_ctx, rw.od, n, H, kqs, s, nullptr, nullptr, 0,
-                       nq, 1, sp);
+                       nq, 1, sp, xk);
     }
   }
   void layer_post(const LayerRows& rw, LayerRun& c, int l, hipStream_t s) {
@@ -1602,17 +1680,23 @@ struct Driver {
       dd.N = dc[i].n_rows;
       dd.T = dc[i].n_cols;
       dd.A = A;
-      dd.n_keys = n_keys;
+      // (the window's own key count; the rows' stride in w stays n_keys)
+      const int nk = slot_keys(dc[i].slot);
+      dd.n_keys = nk;
       dd.seek = seeks[i];
       dd.frames = dc[i].frames;
       dd.cost.resize((size_t)dd.N * dd.T);
       HIPC(hipMemcpyAsync(dd.cost.data(), cost + (size_t)i * cstride, dd.cost.size() * 4,
                           hipMemcpyDeviceToHost, st));
-      dd.probs.resize((size_t)A * dd.N * n_keys);
-      for (int a = 0; a < A; ++a)
+      dd.probs.resize((size_t)A * dd.N * nk);
+      for (int a = 0; a < A && nk == n_keys; ++a)
         HIPC(hipMemcpyAsync(dd.probs.data() + (size_t)a * dd.N * n_keys,
                             w + (size_t)dc[i].slot * wclip + (size_t)a * ncap * n_keys,
                             (size_t)dd.N * n_keys * 4, hipMemcpyDeviceToHost, st));
+      for (int a = 0; a < A && nk != n_keys; ++a)
+        HIPC(hipMemcpy2DAsync(dd.probs.data() + (size_t)a * dd.N * nk, (size_t)nk * 4,
+                              w + (size_t)dc[i].slot * wclip + (size_t)a * ncap * n_keys,
+                              (size_t)n_keys * 4, (size_t)nk * 4, dd.N, hipMemcpyDeviceToHost, st));
       kept = true;
     }
     if (kept) HIPC(hipStreamSynchronize(st));

@@ -28,12 +28,16 @@ namespace mwx {
 
 constexpr int VSTR = 72;  // padded V^T tile row (elements)
 
-template <typename T, int QW = 4>
+// VL: clip b attends over its own lens[b] <= L frames (audio_ctx, DESIGN.md
+// D9): rows and keys >= lens[b] exist in the buffers (the launch shape is the
+// group's L) but no valid row reads them.
+template <typename T, int QW = 4, bool VL = false>
 __global__ __launch_bounds__(64 * QW) void enc_attn_kernel(const _Float16* __restrict__ q,
                                                        const _Float16* __restrict__ k,
                                                        const _Float16* __restrict__ vt, T* __restrict__ o,
-                                                       int H, int L, int Lp, float scale_log2,
-                                                       int nqb) {
+                                                       int H, int Ls, int Lp, float scale_log2,
+                                                       int nqb,
+                                                       const int* __restrict__ lens = nullptr) {
   __shared__ __attribute__((aligned(16))) _Float16 ks[2][64 * 64];
   __shared__ __attribute__((aligned(16))) _Float16 vs[2][64 * VSTR];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -51,8 +55,25 @@ __global__ __launch_bounds__(64 * QW) void enc_attn_kernel(const _Float16* __res
   const int bh = wgid / nqb;
   const int b = bh / H, h = bh - b * H;
   const int q0 = (wgid - bh * nqb) * (32 * QW) + wid * 32;
-  const _Float16* Q = q + (long)bh * L * 64;
-  const _Float16* Kh = k + (long)bh * L * 64;
+  // Ls: rows per clip in the buffers; L: this clip's frames
+  const int L = VL ? min(lens[b], Ls) : Ls;
+  if constexpr (VL) {
+    // a query block past the clip's frames (workgroup-uniform): its output
+    // rows are zero-filled, so the rows past a clip's frames stay finite
+    // through the layer stack, and nothing else runs
+    if ((wgid - bh * nqb) * (32 * QW) >= L) {
+      const int D_ = H * 64;
+      for (int i = threadIdx.x; i < 32 * QW * 8; i += 64 * QW) {
+        const int qi = (wgid - bh * nqb) * (32 * QW) + (i >> 3);
+        if (qi < Ls)
+          *reinterpret_cast<uint4*>(o + ((long)b * Ls + qi) * D_ + h * 64 + (i & 7) * 8) =
+              uint4{0, 0, 0, 0};
+      }
+      return;
+    }
+  }
+  const _Float16* Q = q + (long)bh * Ls * 64;
+  const _Float16* Kh = k + (long)bh * Ls * 64;
   const _Float16* VT = vt + (long)bh * 64 * Lp;
 
   f16x8 qf[2][2];
@@ -225,9 +246,11 @@ __global__ __launch_bounds__(64 * QW) void enc_attn_kernel(const _Float16* __res
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int qi = q0 + u * 16 + c16;
-    if (qi >= L) continue;
+    // (VL: the rows between the clip's frames and the block's end hold the
+    // clamped last query's result: finite, never read by a valid row)
+    if (qi >= Ls) continue;
     const float inv = 1.0f / lrow[u];
-    T* dst = o + ((long)b * L + qi) * D + h * 64;
+    T* dst = o + ((long)b * Ls + qi) * D + h * 64;
 #pragma unroll
     for (int te = 0; te < 4; ++te)
 #pragma unroll
@@ -237,14 +260,18 @@ __global__ __launch_bounds__(64 * QW) void enc_attn_kernel(const _Float16* __res
 
 template <typename T>
 void enc_attention(const _Float16* q, const _Float16* k, const _Float16* vt, T* o, int B, int H,
-                   int L, float scale, hipStream_t st) {
+                   int L, float scale, hipStream_t st, const int* lens) {
   const int Lp = (L + 7) & ~7;
   // (8 waves = 256 queries per workgroup, each K / V tile staged once for
   // twice the queries: measured slower, 704 vs 624 us per large-v3 layer,
   // profiles/r04_ab_regression_beam.md)
   const int nqb = (L + 127) / 128;
-  enc_attn_kernel<T, 4><<<nqb * B * H, 256, 0, st>>>(q, k, vt, o, H, L, Lp,
-                                                    scale * 1.4426950408889634f, nqb);
+  if (lens)
+    enc_attn_kernel<T, 4, true><<<nqb * B * H, 256, 0, st>>>(
+        q, k, vt, o, H, L, Lp, scale * 1.4426950408889634f, nqb, lens);
+  else
+    enc_attn_kernel<T, 4><<<nqb * B * H, 256, 0, st>>>(q, k, vt, o, H, L, Lp,
+                                                      scale * 1.4426950408889634f, nqb);
 }
 
 // ---------------------------------------------------------------------------
@@ -264,14 +291,18 @@ constexpr int DEC_MAX_KEYS = 1536;
 // written to the cache and taken from LDS (its cache line may be stale in L1).
 // The loop body is straight-line (two batches per trip, no early exit), so the
 // compiler keeps exactly one batch in flight with counted vmcnt waits.
-template <typename T, bool SELF, int UBX = 8, bool NTL = !SELF, int NBC = 0>
+// VL (cross): the key count is read per cross slot, xkeys[slot] <= fixed_len
+// (audio_ctx); fixed_len stays the upper bound.
+template <typename T, bool SELF, int UBX = 8, bool NTL = !SELF, int NBC = 0, bool VL = false>
 __global__ __launch_bounds__(256) void dec_attn_kernel(
     const float* __restrict__ P, int KS, int pcols, const float* __restrict__ bias, float qscale,
     float kscale, _Float16* __restrict__ kbase, _Float16* __restrict__ vbase,
     const int* __restrict__ kv_index, const int* __restrict__ pos, const int* __restrict__ active,
     int fixed_len, int cap, T* __restrict__ o, int H, float scale,
     const int* __restrict__ kvmap, const int* __restrict__ own_from, int map_row0, int nq,
-    int R, int write_new = 1, unsigned long long* span = nullptr) {
+    int R, int write_new = 1, unsigned long long* span = nullptr,
+    const int* __restrict__ xkeys = nullptr) {
+  static_assert(!VL || (!SELF && NBC == 0), "VL: the runtime-count cross kernel");
   __shared__ float sc[DEC_MAX_KEYS];
   __shared__ float redf[4];
   __shared__ double redd[4];
@@ -320,7 +351,8 @@ __global__ __launch_bounds__(256) void dec_attn_kernel(
   }
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int kg = lane >> 3, c = lane & 7;
-  const int n = SELF ? p_row + 1 : fixed_len;
+  int n = SELF ? p_row + 1 : fixed_len;
+  if constexpr (VL) n = max(1, min(xkeys[slot], fixed_len));
   const int jnew = SELF ? p_row : -1;
   const int D = H * 64;
   _Float16* K = kbase + (((long)slot * H + h) * cap) * 64;
@@ -673,14 +705,19 @@ void mx_widen_test(const uint8_t* codes, const uint8_t* e8, int n8, uint16_t* ou
 // (wave w: w, w + 4, ...) four at a time, two groups in flight. Round 5: the
 // per-key scale arithmetic after the MFMAs (scores) and on P (P.V) cost ~2/3
 // of the kernel's VALU instructions (PMC, profiles/r05_pmc_xattn_raw.md).
-template <typename T, int NQ, bool KV8 = false, bool NTL = true, int NBC = 0, bool MFS = false>
+// VL: the key count is read per cross slot, xkeys[slot] <= n_max (as
+// dec_attn_kernel's VL).
+template <typename T, int NQ, bool KV8 = false, bool NTL = true, int NBC = 0, bool MFS = false,
+          bool VL = false>
 __global__ __launch_bounds__(256) void dec_xattn_kernel(
     const float* __restrict__ P, int KS, int pcols, const float* __restrict__ bias,
     const void* __restrict__ kbase, const void* __restrict__ vbase,
     const uint8_t* __restrict__ kscale8, const uint8_t* __restrict__ vscale8,
-    const int* __restrict__ kv_index, const int* __restrict__ active, int n, int cap, int R,
-    T* __restrict__ o, int H, float scale, unsigned long long* span = nullptr) {
+    const int* __restrict__ kv_index, const int* __restrict__ active, int n_max, int cap, int R,
+    T* __restrict__ o, int H, float scale, unsigned long long* span = nullptr,
+    const int* __restrict__ xkeys = nullptr) {
   static_assert(!MFS || KV8, "MFS: MX-fp8 caches only");
+  static_assert(!VL || NBC == 0, "VL: a runtime batch count");
   span_start(span);
   __shared__ __attribute__((aligned(16))) float sc[NQ][DEC_MAX_KEYS];
   __shared__ float redf[4][NQ];
@@ -709,6 +746,8 @@ __global__ __launch_bounds__(256) void dec_xattn_kernel(
     span_end(span);
     return;
   }
+  int n = n_max;
+  if constexpr (VL) n = max(1, min(xkeys[slot], n_max));
   const int D = H * 64;
   const long rbase = ((long)slot * H + h) * cap;  // first (time) row of this (slot, head)
   const _Float16* K = reinterpret_cast<const _Float16*>(kbase) + rbase * 64;
@@ -1187,7 +1226,8 @@ bool dec_cross_attention_grouped(const float* P, int KS, int pcols, const float*
                                  const void* kbase, const void* vbase, const int* kv_index,
                                  const int* active, int n_keys, int cap, T* o, int R, int H,
                                  float scale, int nq, hipStream_t st, const uint8_t* kscale8,
-                                 const uint8_t* vscale8, unsigned long long* span) {
+                                 const uint8_t* vscale8, unsigned long long* span,
+                                 const int* xkeys) {
   if (n_keys > DEC_MAX_KEYS || KS > 8) return false;
   const dim3 g(H, (R + nq - 1) / nq);
   const bool kv8 = kscale8 != nullptr;
@@ -1217,7 +1257,19 @@ bool dec_cross_attention_grouped(const float* P, int KS, int pcols, const float*
   switch (nq) {
 #define XQ(N)                                  \
   case N:                                      \
-    if (kv8 && mfs)                            \
+    if (xkeys && kv8 && mfs)                   \
+      dec_xattn_kernel<T, N, true, true, 0, true, true><<<g, 256, 0, st>>>(P, KS, pcols, bias,  \
+          kbase, vbase, kscale8, vscale8, kv_index, active, n_keys, cap, R, o, H, scale, span,  \
+          xkeys);                                                                               \
+    else if (xkeys && kv8)                     \
+      dec_xattn_kernel<T, N, true, true, 0, false, true><<<g, 256, 0, st>>>(P, KS, pcols, bias, \
+          kbase, vbase, kscale8, vscale8, kv_index, active, n_keys, cap, R, o, H, scale, span,  \
+          xkeys);                                                                               \
+    else if (xkeys)                            \
+      dec_xattn_kernel<T, N, false, true, 0, false, true><<<g, 256, 0, st>>>(P, KS, pcols, bias,\
+          kbase, vbase, kscale8, vscale8, kv_index, active, n_keys, cap, R, o, H, scale, span,  \
+          xkeys);                                                                               \
+    else if (kv8 && mfs)                       \
       dec_xattn_kernel<T, N, true, true, 0, true><<<g, 256, 0, st>>>(P, KS, pcols, bias, kbase, \
           vbase, kscale8, vscale8, kv_index, active, n_keys, cap, R, o, H, scale, span);       \
     else if (kv8 && nt)                        \
@@ -1239,12 +1291,14 @@ template bool dec_cross_attention_grouped<_Float16>(const float*, int, int, cons
                                                     const void*, const void*, const int*,
                                                     const int*, int, int, _Float16*, int, int,
                                                     float, int, hipStream_t, const uint8_t*,
-                                                    const uint8_t*, unsigned long long*);
+                                                    const uint8_t*, unsigned long long*,
+                                                    const int*);
 template bool dec_cross_attention_grouped<__bf16>(const float*, int, int, const float*,
                                                   const void*, const void*, const int*,
                                                   const int*, int, int, __bf16*, int, int, float,
                                                   int, hipStream_t, const uint8_t*,
-                                                  const uint8_t*, unsigned long long*);
+                                                  const uint8_t*, unsigned long long*,
+                                                  const int*);
 
 // Prompt prefill: the self-attention K / V of every (virtual) row appended
 // to its cache row crow[row] at position pos[row] before the self-attention
@@ -1299,7 +1353,8 @@ void dec_attention(const float* P, int KS, int pcols, const float* bias, float q
                    float kscale, _Float16* kbase, _Float16* vbase, const int* kv_index,
                    const int* pos, const int* active, int fixed_len, int kv_len_cap, T* o, int R,
                    int H, float scale, hipStream_t st, const int* kvmap, const int* own_from,
-                   int map_row0, int nq, int write_new, unsigned long long* span) {
+                   int map_row0, int nq, int write_new, unsigned long long* span,
+                   const int* xkeys) {
   dim3 g(H, R);
   if (nq > 1 && R % nq == 0) {
     const int groups = (R / nq) * H;
@@ -1322,7 +1377,15 @@ void dec_attention(const float* P, int KS, int pcols, const float* bias, float q
   // MWX_XATTN_NBC=0: the runtime-batch-count cross kernel (A/B of the
   // constant-count load stream)
   static const bool xattn_nbc = !(getenv("MWX_XATTN_NBC") && atoi(getenv("MWX_XATTN_NBC")) == 0);
-  if (fixed_len == 0 && self_ub4)
+  if (fixed_len != 0 && xkeys && xattn_nt)
+    dec_attn_kernel<T, false, 8, true, 0, true><<<g, 256, 0, st>>>(
+        P, KS, pcols, bias, qscale, kscale, kbase, vbase, kv_index, pos, active, fixed_len,
+        kv_len_cap, o, H, scale, nullptr, nullptr, 0, nq, R, 1, span, xkeys);
+  else if (fixed_len != 0 && xkeys)
+    dec_attn_kernel<T, false, 8, false, 0, true><<<g, 256, 0, st>>>(
+        P, KS, pcols, bias, qscale, kscale, kbase, vbase, kv_index, pos, active, fixed_len,
+        kv_len_cap, o, H, scale, nullptr, nullptr, 0, nq, R, 1, span, xkeys);
+  else if (fixed_len == 0 && self_ub4)
     dec_attn_kernel<T, true, 4><<<g, 256, 0, st>>>(P, KS, pcols, bias, qscale, kscale, kbase,
                                                    vbase, kv_index, pos, active, fixed_len,
                                                    kv_len_cap, o, H, scale, kvmap, own_from,
@@ -1355,16 +1418,16 @@ void dec_attention(const float* P, int KS, int pcols, const float* bias, float q
 }
 
 template void enc_attention<_Float16>(const _Float16*, const _Float16*, const _Float16*, _Float16*,
-                                      int, int, int, float, hipStream_t);
+                                      int, int, int, float, hipStream_t, const int*);
 template void enc_attention<__bf16>(const _Float16*, const _Float16*, const _Float16*, __bf16*, int,
-                                    int, int, float, hipStream_t);
+                                    int, int, float, hipStream_t, const int*);
 template void dec_attention<_Float16>(const float*, int, int, const float*, float, float,
                                       _Float16*, _Float16*, const int*, const int*, const int*, int,
                                       int, _Float16*, int, int, float, hipStream_t, const int*,
-                                      const int*, int, int, int, unsigned long long*);
+                                      const int*, int, int, int, unsigned long long*, const int*);
 template void dec_attention<__bf16>(const float*, int, int, const float*, float, float, _Float16*,
                                     _Float16*, const int*, const int*, const int*, int, int,
                                     __bf16*, int, int, float, hipStream_t, const int*, const int*, int, int,
-                                    int, unsigned long long*);
+                                    int, unsigned long long*, const int*);
 
 }  // namespace mwx

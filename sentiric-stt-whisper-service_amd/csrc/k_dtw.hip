@@ -19,13 +19,14 @@ namespace mwx {
 // (f32 max, expf, double sum in block_sum_256d's order) but its f32
 // probabilities are kept (the decoder rounds them to f16 for P.V). A row below
 // pos0 (the sot sequence) or inactive (padding) writes nothing.
-template <bool KV8>
+// VL: slot's key count xkeys[slot] <= n_max; the output row stride stays n_max.
+template <bool KV8, bool VL = false>
 __global__ __launch_bounds__(256) void align_qk_kernel(
     const float* __restrict__ P, int KS, int pcols, const float* __restrict__ bias, float qscale,
     float scale, const void* __restrict__ kbase, const uint8_t* __restrict__ kscale8,
     const int* __restrict__ kv_index, const int* __restrict__ pos, const int* __restrict__ active,
-    const int2* __restrict__ heads, int n, int cap, int R, int H, int pos0, int A, int n_rows_cap,
-    float* __restrict__ out) {
+    const int2* __restrict__ heads, int n_max, int cap, int R, int H, int pos0, int A,
+    int n_rows_cap, float* __restrict__ out, const int* __restrict__ xkeys = nullptr) {
   __shared__ float sc[DTW_MAX_KEYS];
   __shared__ float redf[4];
   __shared__ double redd[4];
@@ -37,6 +38,8 @@ __global__ __launch_bounds__(256) void align_qk_kernel(
   const int2 ha = heads[blockIdx.x];
   const int orow = p_row - pos0;
   if (!act_r || orow < 0 || orow >= n_rows_cap) return;
+  int n = n_max;
+  if constexpr (VL) n = max(1, min(xkeys[slot], n_max));
   const int h = ha.x;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int kg = lane >> 3, c = lane & 7;
@@ -92,7 +95,7 @@ __global__ __launch_bounds__(256) void align_qk_kernel(
   }
   sum = block_sum_256d(sum, redd);
   const float inv = (float)(1.0 / sum);
-  float* o = out + (((long)slot * A + ha.y) * n_rows_cap + orow) * n;
+  float* o = out + (((long)slot * A + ha.y) * n_rows_cap + orow) * n_max;
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const int j = tid + 256 * i;
@@ -103,11 +106,19 @@ __global__ __launch_bounds__(256) void align_qk_kernel(
 bool align_probs(const float* P, int KS, int pcols, const float* bias, float qscale, float scale,
                  const void* kbase, const uint8_t* kscale8, const int* kv_index, const int* pos,
                  const int* active, const int2* heads, int n_heads, int n_keys, int cap, int R, int H,
-                 int pos0, int A, int n_rows_cap, float* out, hipStream_t st) {
+                 int pos0, int A, int n_rows_cap, float* out, hipStream_t st, const int* xkeys) {
   if (n_keys < 1 || n_keys > DTW_MAX_KEYS || n_keys > cap || KS < 1 || R < 1 || n_heads < 1)
     return false;
   const dim3 grid(n_heads, R);
-  if (kscale8)
+  if (xkeys && kscale8)
+    align_qk_kernel<true, true><<<grid, 256, 0, st>>>(P, KS, pcols, bias, qscale, scale, kbase,
+                                                      kscale8, kv_index, pos, active, heads, n_keys,
+                                                      cap, R, H, pos0, A, n_rows_cap, out, xkeys);
+  else if (xkeys)
+    align_qk_kernel<false, true><<<grid, 256, 0, st>>>(P, KS, pcols, bias, qscale, scale, kbase,
+                                                       nullptr, kv_index, pos, active, heads, n_keys,
+                                                       cap, R, H, pos0, A, n_rows_cap, out, xkeys);
+  else if (kscale8)
     align_qk_kernel<true><<<grid, 256, 0, st>>>(P, KS, pcols, bias, qscale, scale, kbase, kscale8,
                                                 kv_index, pos, active, heads, n_keys, cap, R, H,
                                                 pos0, A, n_rows_cap, out);

@@ -70,7 +70,8 @@ __device__ __forceinline__ void epi_store(const EpiParams& P, int bz, int m, int
     const int nn = r - kv * d;
     const int h = nn >> 6, e = nn & 63;
     const int bl = m / P.L, t = m - bl * P.L;
-    const long idx = ((((long)layer * P.ncap + P.slot[bl]) * P.H + h) * P.L + t) * 64 + e;
+    const long idx =
+        ((((long)layer * P.ncap + P.slot[bl]) * P.H + h) * P.lcap + t) * 64 + e;
     if (!kv)
       P.k[idx] = f16r(acc * P.kscale);
     else
@@ -664,7 +665,8 @@ __global__ __launch_bounds__(512, 1) void gemm_big(const void* __restrict__ Av, 
               // values is two MX blocks of 32 (4 lanes x 8 values each):
               // block amax over the 4 lanes, E8M0 exponent, e4m3 codes
               const int b = m / P.L, t = m - b * P.L;
-              const long ridx = (((long)layer * P.ncap + P.slot[b]) * P.H + h) * P.L + t;
+              const long ridx =
+                  (((long)layer * P.ncap + P.slot[b]) * P.H + h) * P.lcap + t;
               const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
               float f[8];
               float amax = 0.0f;
@@ -697,7 +699,8 @@ __global__ __launch_bounds__(512, 1) void gemm_big(const void* __restrict__ Av, 
               dst = (part == 0 ? P.q : P.k) + (((long)b * P.H + h) * P.L + t) * 64 + ch * 8;
             } else {
               const long idx =
-                  ((((long)layer * P.ncap + P.slot[b]) * P.H + h) * P.L + t) * 64 + ch * 8;
+                  ((((long)layer * P.ncap + P.slot[b]) * P.H + h) * P.lcap + t) * 64 +
+                  ch * 8;
               dst = (part ? P.v : P.k) + idx;
             }
           }

@@ -203,17 +203,22 @@ __global__ __launch_bounds__(256) void mel_norm_kernel(float* __restrict__ mel_b
 __global__ __launch_bounds__(256) void mel_window_kernel(
     const float* __restrict__ mel, long mel_clip_stride, const int* __restrict__ clip_of_slot,
     const int* __restrict__ seek_of_slot, const int* __restrict__ n_len_of_slot, int n_mels,
-    int T, int cpad, _Float16* __restrict__ melT) {
+    int T, int cpad, _Float16* __restrict__ melT, const int* __restrict__ n_ctx_of_slot) {
   __shared__ float tile[64][65];
   const int slot = blockIdx.z;
   const int t0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
   const float* src = mel + (long)clip_of_slot[slot] * mel_clip_stride;
-  const int seek = seek_of_slot[slot], n_len = n_len_of_slot[slot];
+  const int seek = seek_of_slot[slot];
+  // a slot with its own audio context reads 2 n_ctx frames of its window; the
+  // frames past them are zero, as the conv padding of a window that long
+  const int n_len = n_ctx_of_slot ? min(n_len_of_slot[slot], seek + 2 * n_ctx_of_slot[slot])
+                                  : n_len_of_slot[slot];
+  const int n_stride = n_len_of_slot[slot];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   for (int r = ty; r < 64; r += 4) {
     const int c = c0 + r, t = t0 + tx;
     float v = 0.0f;
-    if (c < n_mels && t < T && seek + t < n_len) v = src[(long)c * n_len + seek + t];
+    if (c < n_mels && t < T && seek + t < n_len) v = src[(long)c * n_stride + seek + t];
     tile[r][tx] = v;
   }
   __syncthreads();
@@ -254,10 +259,11 @@ void launch_mel_batch(const float* pcm_base, const MelClip* desc, int n_clips, i
 }
 void launch_mel_window(const float* mel, long mel_clip_stride, const int* clip_of_slot,
                        const int* seek_of_slot, const int* n_len_of_slot, int n_mels, int T,
-                       int cpad, _Float16* melT, int n_slots, hipStream_t st) {
+                       int cpad, _Float16* melT, int n_slots, hipStream_t st,
+                       const int* n_ctx_of_slot) {
   dim3 g((T + 63) / 64, (cpad + 63) / 64, n_slots);
   mel_window_kernel<<<g, 256, 0, st>>>(mel, mel_clip_stride, clip_of_slot, seek_of_slot,
-                                       n_len_of_slot, n_mels, T, cpad, melT);
+                                       n_len_of_slot, n_mels, T, cpad, melT, n_ctx_of_slot);
 }
 // pcm16 -> f32 as SttEngine::transcribe_pcm16 converts (x / 32768, exact)
 __global__ void pcm16_to_f32_kernel(const int16_t* __restrict__ in, long n, float* __restrict__ out) {

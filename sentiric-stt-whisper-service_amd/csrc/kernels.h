@@ -40,6 +40,7 @@ struct EpiParams {
   int d = 0;     // model width
   int ncap = 0;  // slots in the cross / self cache
   int ldv = 0;   // encoder V^T row stride (padded L)
+  int lcap = 0;  // EPI_CROSS_KV: (time) rows of a cache slot (always set); L = rows per clip of A
   const int* pos = nullptr;     // decoder: position per row
   const int* active = nullptr;  // decoder: row active flag
   const int* slot = nullptr;    // cross: cache slot per encoder batch index
@@ -179,7 +180,8 @@ void launch_mel_batch(const float* pcm_base, const MelClip* desc, int n_clips, i
                       float* part, float* mx, hipStream_t st);
 void launch_mel_window(const float* mel, long mel_clip_stride, const int* clip_of_slot,
                        const int* seek_of_slot, const int* n_len_of_slot, int n_mels, int T,
-                       int cpad, _Float16* melT, int n_slots, hipStream_t st);
+                       int cpad, _Float16* melT, int n_slots, hipStream_t st,
+                       const int* n_ctx_of_slot = nullptr);
 void launch_signal_energy(const float* x, int n, float* out, hipStream_t st);
 // pcm16 / 32768 -> f32 (in and out 8- / 16-byte aligned)
 void launch_pcm16_to_f32(const int16_t* in, long n, float* out, hipStream_t st);
@@ -213,9 +215,11 @@ void layer_norm_dec(float* x, const float* w, const float* b, T* y, int M, int N
 
 
 // encoder self-attention: q,k [B][H][L][64], vt [B][H][64][L] f16 -> o [B*L][H*64] (T)
+// lens != nullptr (device, [B]): clip b attends over its first lens[b] <= L
+// frames only; its rows >= lens[b] of o are written (finite) but mean nothing.
 template <typename T>
 void enc_attention(const _Float16* q, const _Float16* k, const _Float16* vt, T* o, int B,
-                   int H, int L, float scale, hipStream_t st);
+                   int H, int L, float scale, hipStream_t st, const int* lens = nullptr);
 
 // decode attention for R rows: q [R][H*64] f16; K/V rows [n_keys][64] per
 // (row, head). self: K = kbase + ((row*H + h)*kstride_rows)*64, n_keys =
@@ -230,13 +234,16 @@ void enc_attention(const _Float16* q, const _Float16* k, const _Float16* vt, T* 
 // row `row` is read from the cache of row kvmap[row * kv_len_cap + j] - map_row0.
 // cross: nq > 1 = rows come in groups of nq sharing one slot (beam / best-of
 // decoders of a clip); their workgroups are co-scheduled on one XCD.
+// cross, xkeys != nullptr (device, per cross slot): the row attends over the
+// first xkeys[slot] <= fixed_len keys of its slot.
 template <typename T>
 void dec_attention(const float* P, int KS, int pcols, const float* bias, float qscale,
                    float kscale, _Float16* kbase, _Float16* vbase, const int* kv_index,
                    const int* pos, const int* active, int fixed_len, int kv_len_cap, T* o, int R,
                    int H, float scale, hipStream_t st, const int* kvmap = nullptr,
                    const int* own_from = nullptr, int map_row0 = 0, int nq = 1,
-                   int write_new = 1, unsigned long long* span = nullptr);
+                   int write_new = 1, unsigned long long* span = nullptr,
+                   const int* xkeys = nullptr);
 
 // Prompt prefill: K / V of every row (reduced from the QKV slabs exactly as
 // dec_attention's self kernel reduces its own position) appended to cache row
@@ -269,7 +276,8 @@ bool dec_cross_attention_grouped(const float* P, int KS, int pcols, const float*
                                  float scale, int nq, hipStream_t st,
                                  const uint8_t* kscale8 = nullptr,
                                  const uint8_t* vscale8 = nullptr,
-                                 unsigned long long* span = nullptr);
+                                 unsigned long long* span = nullptr,
+                                 const int* xkeys = nullptr);
 
 // DTW token timestamps (k_dtw.hip).
 constexpr int DTW_MAX_KEYS = 1536;  // encoder frames (n_audio_ctx)
@@ -280,11 +288,14 @@ constexpr int DTW_MAX_ROWS = 256;   // alignment rows of a window (NOT + text to
 // f16((sum of the KS slabs of P + bias) * qscale), into
 // out[((kv_index[r] * A + a) * n_rows_cap + pos[r] - pos0) * n_keys ..]. kscale8
 // != nullptr: MX-fp8 cache (as dec_cross_attention_grouped). false: arguments
-// outside the kernel's limits (nothing launched).
+// outside the kernel's limits (nothing launched). xkeys != nullptr (device,
+// per cross slot): the softmax runs over the first xkeys[slot] <= n_keys keys
+// and only those columns of the row (stride n_keys) are written.
 bool align_probs(const float* P, int KS, int pcols, const float* bias, float qscale, float scale,
                  const void* kbase, const uint8_t* kscale8, const int* kv_index, const int* pos,
                  const int* active, const int2* heads, int n_heads, int n_keys, int cap, int R, int H,
-                 int pos0, int A, int n_rows_cap, float* out, hipStream_t st);
+                 int pos0, int A, int n_rows_cap, float* out, hipStream_t st,
+                 const int* xkeys = nullptr);
 // cost[b][n][t] = -mean_a median7_t((w - mean_n) / std_n) over the first Ts[b]
 // columns and Ns[b] rows of clip b's probabilities (slot slot_of[b] of w, laid
 // out as align_probs writes it); clip b's matrix at cost + b * cost_stride,

@@ -314,6 +314,14 @@ long mwx_stt_batches(void* eng) { return static_cast<SttEngine*>(eng)->batches_r
 
 void mwx_stt_free(void* eng) { delete static_cast<SttEngine*>(eng); }
 
+// Settings::audio_ctx / audio_ctx_fit of the requests that start after the
+// call, on every request path of the engine. 0; -1 without an engine or for
+// an audio_ctx above 1500 frames (nothing changes).
+int mwx_stt_set_audio_ctx(void* eng, int audio_ctx, int fit) {
+  if (!eng) return -1;
+  return static_cast<SttEngine*>(eng)->set_audio_ctx(audio_ctx, fit != 0) ? 0 : -1;
+}
+
 // 0.. = JSON length written; -1 = error; -2 = EngineBusyException;
 // < -2 = -(needed capacity). abort_after >= 0: RequestOptions::should_abort
 // answers true from its (abort_after + 1)-th call on (the service's abort

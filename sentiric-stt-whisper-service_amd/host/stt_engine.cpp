@@ -418,6 +418,8 @@ mwx_full_params SttEngine::make_params(const RequestOptions& options, std::strin
   p.entropy_thold = 2.40f;
   p.logprob_thold = settings_.logprob_threshold;
   p.n_threads = settings_.n_threads;
+  p.audio_ctx = settings_.audio_ctx;
+  p.audio_ctx_fit = settings_.audio_ctx_fit;
   return p;
 }
 

@@ -91,6 +91,14 @@ struct Settings {
   int dtw_aheads_preset = 0;
   int dtw_n_top = -1;
   std::vector<std::pair<int, int>> dtw_aheads;
+  // Audio context (mwx_full_params.audio_ctx / audio_ctx_fit; DESIGN.md D9,
+  // INTEGRATION.md "Audio context"), for every request path. audio_ctx > 0:
+  // every window is encoded to that many frames; audio_ctx_fit: every window
+  // to the frames its remaining audio needs (audio_ctx the floor). Both off
+  // by default: the effect of a short context on recognition quality is
+  // unmeasured.
+  int audio_ctx = 0;
+  bool audio_ctx_fit = false;
 };
 
 // Reads the DTW settings from the environment, as the service reads its other
@@ -199,6 +207,16 @@ class SttEngine {
 
   bool is_ready() const { return ctx_ != nullptr; }
   const Settings& get_settings() const { return settings_; }
+  // Settings::audio_ctx / audio_ctx_fit of the requests that start after the
+  // call (not synchronized with requests in flight: set it before serving).
+  // false, and nothing changed, for more than kMaxAudioCtx frames.
+  static constexpr int kMaxAudioCtx = 1500;  // every Whisper model's n_audio_ctx
+  bool set_audio_ctx(int audio_ctx, bool fit) {
+    if (audio_ctx > kMaxAudioCtx) return false;
+    settings_.audio_ctx = audio_ctx > 0 ? audio_ctx : 0;
+    settings_.audio_ctx_fit = fit;
+    return true;
+  }
 
   struct PerformanceMetrics {
     double queue_time_ms;

@@ -111,6 +111,7 @@ class FullParams(C.Structure):
         ("greedy", _Greedy), ("beam_search", _Beam),
         ("abort_callback", ABORT_CB), ("abort_callback_user_data", C.c_void_p),
         ("bench_fixed_steps", C.c_int),
+        ("audio_ctx_fit", C.c_bool),
     ]
 
 
@@ -214,6 +215,8 @@ def lib() -> C.CDLL:
         f = getattr(L, f"mwx_{n}")
         f.restype = C.c_int
         f.argtypes = [P]
+    L.mwx_audio_ctx_for.restype = C.c_int
+    L.mwx_audio_ctx_for.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_bool]
     L.mwx_model_quantize.restype = C.c_int
     L.mwx_model_quantize.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
     L.mwx_write_synthetic_model.restype = C.c_int
@@ -231,6 +234,10 @@ def lib() -> C.CDLL:
     L.mwx_test_encode.restype = C.c_int
     L.mwx_test_encode.argtypes = [P, P, C.POINTER(C.c_float), C.c_int, C.c_int,
                                   C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.mwx_test_encode_ctx.restype = C.c_int
+    L.mwx_test_encode_ctx.argtypes = [P, P, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int,
+                                      C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float)]
     L.mwx_test_decode.restype = C.c_int
     L.mwx_test_decode.argtypes = [P, P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float)]
     L.mwx_test_decode_last.restype = C.c_int
@@ -759,6 +766,29 @@ class Context:
                                   fptr(k) if cross else null, fptr(v) if cross else null)
         if r != 0:
             raise RuntimeError(f"mwx_test_encode returned {r}")
+        return enc, k, v
+
+    def audio_ctx_for(self, n_samples: int, seek: int = 0, audio_ctx: int = 0,
+                      fit: bool = False) -> int:
+        """mwx_audio_ctx_for: the audio context of the window at `seek` of a
+        clip of n_samples samples under FullParams.audio_ctx / audio_ctx_fit."""
+        return lib().mwx_audio_ctx_for(self.ctx, int(n_samples), int(seek), int(audio_ctx),
+                                       bool(fit))
+
+    def test_encode_ctx(self, pcm: np.ndarray, audio_ctx: int, seek: int = 0,
+                        state_index: int = 0):
+        """mwx_test_encode_ctx: test_encode at an audio context of audio_ctx
+        frames (enc [K][d], k / v [n_text_layer][K][d]); the cross K/V and the
+        key count stay in the state for test_decode*."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        K, d, nl = int(audio_ctx), self.d, self.n_text_layer
+        enc = np.empty((K, d), dtype=np.float32)
+        k = np.empty((nl, K, d), dtype=np.float32)
+        v = np.empty((nl, K, d), dtype=np.float32)
+        r = lib().mwx_test_encode_ctx(self.ctx, self.state(state_index), fptr(pcm), len(pcm), seek,
+                                      K, fptr(enc), fptr(k), fptr(v))
+        if r != 0:
+            raise RuntimeError(f"mwx_test_encode_ctx returned {r}")
         return enc, k, v
 
     def test_encode_dump(self, pcm: np.ndarray, seek: int = 0, state_index: int = 0):
