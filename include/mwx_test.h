@@ -203,6 +203,96 @@ int mwx_test_gemm_dec(struct mwx_context* ctx, int bf16, int mode, int M, int N,
                       const float* a, const float* w, const float* bias, const float* res,
                       int* ks_out, float* out);
 
+/* --- encoder kernels on given data (tests/test_gpu_encoder_kernels.py) ------
+ * Every hook below checks every size and index on the host (-1 without a
+ * launch), keeps each device output between two guard bands of sentinel words
+ * (-3 if a launch changed one), and returns -2 on a device error and -4 for a
+ * shape the kernel family does not serve. bf16 selects the kernels' 16-bit
+ * type T (bf16 or f16) whatever the context's model holds. */
+
+/* One enc_attention<T> launch. q, k: f16 bits [B][H][L][64]; vt: f16 bits
+ * [B][H][64][Lp], Lp = (L + 7) & ~7, the pad columns [L, Lp) supplied by the
+ * caller; lens (nullable) [B]: clip b attends over its first lens[b] frames
+ * (the VL instantiation). o: f32 [B L][H 64] = the T output widened; a word
+ * the launch did not write is NaN. The kernel reads the V^T columns [L, Lp)
+ * (under lens: [lens[b], L) too) and multiplies them by an exact zero: they
+ * must be finite (never NaN or Inf); Q and K rows >= lens[b] are never read.
+ * -1 unless B H <= 64, 1 <= L <= 1536 and every lens[b] in 1 .. L. */
+int mwx_test_enc_attn(struct mwx_context* ctx, int bf16, int B, int H, int L, const int* lens,
+                      float scale, const uint16_t* q, const uint16_t* k, const uint16_t* vt,
+                      float* o);
+
+/* One encoder GEMM launch (gemm<T>, the 256 x 256 tile kernel with its staged
+ * epilogues). a (a_len floats) and w [N][K] are rounded to T on the host; row m
+ * of batch z of A starts at a + z a_bstride + m lda (rows may overlap, lda < K:
+ * the conv stem's im2col view). epi is the EPI_* value of csrc/kernels.h:
+ *   1 EPI_GELU   c16 (c_len 16-bit words, in and out) receives
+ *                T(gelu_ggml(acc + bias)) (out16 != 0: f16 whatever T is) at
+ *                c_off + z c_bstride + m ldc + n; use_table: the GELU table.
+ *   2 EPI_RES    c32 (c_len floats, in and out; the residual is read in place
+ *                as the engine calls it) = (acc + bias) + c32, bias nullable.
+ *   3 EPI_CONV2  c32 = pe[m][n] + gelu_ggml(acc + bias), pe [M][ldc].
+ *   0 EPI_ENC_QKV  N = 3 d, H 64 = d: q, k f16 bits [M / L][H][L][64] and v =
+ *                V^T [M / L][H][64][ldv] (in and out: the columns >= L keep
+ *                what the caller put there). -1 unless L % 4 == 0, M % L == 0,
+ *                ldv % 4 == 0, ldv >= L (the 8-byte V^T stores).
+ *   5 EPI_CROSS_KV N = layers 2 d: k, v f16 bits [layers][ncap][H][lcap][64] (in
+ *                and out), clip b = m / L goes to slot[b] (injective, in
+ *                [0, ncap)), K = f16(acc kscale), V = f16(acc + bias). With
+ *                kv8 != 0 the cache is MX-fp8 instead: k8, v8 e4m3 codes in
+ *                that shape and ks8, vs8 [layers][ncap][H][lcap][2] E8M0 scales
+ *                (one per 32-element half), all in and out; k, v unused.
+ * mx != 0: the MX-fp8 compute mode, mx_quantize<T> of the T-rounded a (dense:
+ * lda = K, batch = 1) followed by gemm_mx<T> on w quantized by the load-time
+ * host quantizer, as mwx_test_gemm_mx runs it; K % 128 == 0, epi 0, 1 (T
+ * output), 2 or 5.
+ * -1 unless M <= 4096, N <= 2048, K <= 5120, batch <= 8, K % 64 == 0,
+ * N % 64 == 0, d % 64 == 0, lda, a_bstride, ldc, c_bstride and c_off are
+ * multiples of 8 (16-byte vector accesses), the last A element read lies
+ * inside a_len and the last output inside c_len. */
+struct mwx_test_gemm_enc_args {
+  int bf16, epi, out16, use_table, mx, kv8;
+  int M, N, K, batch;
+  long lda, a_bstride, a_len;
+  long ldc, c_bstride, c_off, c_len;
+  int L, H, d, ldv, lcap, ncap;
+  float kscale;
+  const float* a;
+  const float* w;
+  const float* bias;
+  const float* pe;
+  const int* slot;
+  uint16_t* c16;
+  float* c32;
+  uint16_t* q;
+  uint16_t* k;
+  uint16_t* v;
+  uint8_t* k8;
+  uint8_t* v8;
+  uint8_t* ks8;
+  uint8_t* vs8;
+};
+int mwx_test_gemm_enc(struct mwx_context* ctx, const struct mwx_test_gemm_enc_args* args);
+
+/* layer_norm<T> (dec == 0) or layer_norm_dec<T> (dec != 0) on x [M][N] (in
+ * and out), w, b [N], active (nullable) [M], P (nullable) [KS][M][N] with
+ * pbias [N]. dec with te != NULL (EmbedIn): x is first formed as
+ * T(te[tok[r]]) + pe[pos[r]], te [n_tok][N] (rounded to T), pe [n_pos][N],
+ * tok / pos [M] (any value: the kernel clamps them). y [M][N] f32 = the T
+ * output (dec: unpacked from the pack_index layout); a row the launch did not
+ * write is NaN. -4 for N > 2048 (layer_norm launches nothing there) and, dec,
+ * N % 32 != 0 (pack_index tiles are 32 deep). -1 unless M <= 1024, KS 1 .. 8. */
+int mwx_test_layer_norm(struct mwx_context* ctx, int bf16, int dec, int M, int N, float* x,
+                        const float* w, const float* b, const int* active, const float* P, int KS,
+                        const float* pbias, const float* te, const float* pe, const int* tok,
+                        const int* pos, int n_tok, int n_pos, float* y);
+
+/* The context's device-built f16 GELU table: entry i < 0x4901 = the f16 bits
+ * of gelu(h) for the f16 h with bits i, entry 0x4901 + i for bits 0x8000 | i.
+ * out receives mwx_test_gelu_table_size() words. */
+int mwx_test_gelu_table_size(void);
+int mwx_test_gelu_table(struct mwx_context* ctx, uint16_t* out);
+
 /* vad_segments_kernel on caller-supplied probabilities: clip b has
  * mwx_vad_n_chunks(n_samples[b]) of them at probs + probs_offset[b] and its own
  * params[b]. Out: n_segments[b], compact_len[b], its segments as (start, end)

@@ -2933,6 +2933,341 @@ extern "C" int mwx_test_gemm_dec(struct mwx_context* ctx, int bf16, int mode, in
 }
 
 // ---------------------------------------------------------------------------
+// Encoder kernels on given data (mwx_test_enc_attn / _gemm_enc / _layer_norm)
+// ---------------------------------------------------------------------------
+// A device output of `bytes` bytes between two guard bands of TEST_GUARD_WORD
+// (the slack up to the next 16 bytes belongs to the upper band). The body
+// starts as `init` (in-and-out buffers) or as all-ones bits: NaN as f16, bf16
+// and f32, so a word no launch wrote reads back NaN.
+struct GuardedBuf {
+  uint8_t* dev = nullptr;
+  size_t bytes = 0, total = 0;
+  static constexpr size_t G = TEST_GUARD_WORDS * 4;
+  void* make(DevScratch& m, size_t n, const void* init) {
+    bytes = n;
+    total = 2 * G + (n + 15) / 16 * 16;
+    std::vector<uint32_t> img(total / 4, TEST_GUARD_WORD);
+    if (init)
+      memcpy((uint8_t*)img.data() + G, init, n);
+    else
+      memset((uint8_t*)img.data() + G, 0xff, n);
+    dev = (uint8_t*)m.get(total);
+    HIPC(hipMemcpy(dev, img.data(), total, hipMemcpyHostToDevice));
+    return dev + G;
+  }
+  // copies the body to out; false if a band changed
+  bool take(void* out) const {
+    std::vector<uint32_t> img(total / 4);
+    HIPC(hipMemcpy(img.data(), dev, total, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> want(total / 4, TEST_GUARD_WORD);
+    memcpy((uint8_t*)want.data() + G, (const uint8_t*)img.data() + G, bytes);
+    if (memcmp(want.data(), img.data(), total)) return false;
+    memcpy(out, (const uint8_t*)img.data() + G, bytes);
+    return true;
+  }
+};
+
+template <typename T>
+static int test_enc_attn_impl(int B, int H, int L, const int* lens, float scale,
+                              const uint16_t* q, const uint16_t* k, const uint16_t* vt, float* o) {
+  const int Lp = (L + 7) & ~7;
+  const size_t qb = (size_t)B * H * L * 64 * 2, vb = (size_t)B * H * 64 * Lp * 2;
+  const size_t on = (size_t)B * L * H * 64;
+  DevScratch m;
+  void* dq = m.get(qb);
+  void* dk = m.get(qb);
+  void* dv = m.get(vb);
+  void* dl = lens ? m.get((size_t)B * 4) : nullptr;
+  GuardedBuf og;
+  void* dout = og.make(m, on * 2, nullptr);
+  HIPC(hipMemcpy(dq, q, qb, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(dk, k, qb, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(dv, vt, vb, hipMemcpyHostToDevice));
+  if (dl) HIPC(hipMemcpy(dl, lens, (size_t)B * 4, hipMemcpyHostToDevice));
+  mwx::enc_attention<T>((const _Float16*)dq, (const _Float16*)dk, (const _Float16*)dv, (T*)dout, B,
+                        H, L, scale, nullptr, (const int*)dl);
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  std::vector<uint16_t> ob(on);
+  if (!og.take(ob.data())) return -3;
+  const bool bf = std::is_same<T, __bf16>::value;
+  for (size_t i = 0; i < on; ++i) o[i] = bf ? mwx::bf16_to_f32(ob[i]) : mwx::f16_to_f32(ob[i]);
+  return 0;
+}
+
+extern "C" int mwx_test_enc_attn(struct mwx_context* ctx, int bf16, int B, int H, int L,
+                                 const int* lens, float scale, const uint16_t* q,
+                                 const uint16_t* k, const uint16_t* vt, float* o) {
+  if (!ctx || !q || !k || !vt || !o) return -1;
+  if (B < 1 || H < 1 || (long)B * H > 64 || L < 1 || L > 1536) return -1;
+  if (lens)
+    for (int b = 0; b < B; ++b)
+      if (lens[b] < 1 || lens[b] > L) return -1;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    if (bf16) return test_enc_attn_impl<__bf16>(B, H, L, lens, scale, q, k, vt, o);
+    return test_enc_attn_impl<_Float16>(B, H, L, lens, scale, q, k, vt, o);
+  } catch (...) {
+    return -2;
+  }
+}
+
+template <typename T>
+static int test_gemm_enc_impl(struct mwx_context* ctx, const mwx_test_gemm_enc_args& g) {
+  const bool bf = std::is_same<T, __bf16>::value;
+  auto cvt = [&](float f) { return bf ? mwx::f32_to_bf16(f) : mwx::f32_to_f16(f); };
+  std::vector<uint16_t> ah((size_t)g.a_len), wh((size_t)g.N * g.K);
+  for (size_t i = 0; i < ah.size(); ++i) ah[i] = cvt(g.a[i]);
+  for (size_t i = 0; i < wh.size(); ++i) wh[i] = cvt(g.w[i]);
+  DevScratch m;
+  void* da = m.get(ah.size() * 2);
+  HIPC(hipMemcpy(da, ah.data(), ah.size() * 2, hipMemcpyHostToDevice));
+  mwx::EpiParams e;
+  void *dw, *dq = nullptr;
+  if (g.mx) {
+    // w by the load-time host quantizer, a by the device kernel (dense [M][K])
+    std::vector<uint8_t> wq((size_t)g.N * g.K), ws((size_t)g.N * (g.K / 32));
+    std::vector<float> row(g.K);
+    for (int n = 0; n < g.N; ++n) {
+      for (int k = 0; k < g.K; ++k) {
+        const uint16_t h = wh[(size_t)n * g.K + k];
+        row[k] = bf ? mwx::bf16_to_f32(h) : mwx::f16_to_f32(h);
+      }
+      mwx::mx_quantize_row(row.data(), g.K, wq.data() + (size_t)n * g.K,
+                           ws.data() + (size_t)n * (g.K / 32));
+    }
+    dw = m.get(wq.size());
+    void* dsw = m.get(ws.size());
+    dq = m.get((size_t)g.M * g.K);
+    void* dsa = m.get((size_t)g.M * (g.K / 32));
+    HIPC(hipMemcpy(dw, wq.data(), wq.size(), hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dsw, ws.data(), ws.size(), hipMemcpyHostToDevice));
+    mwx::mx_quantize<T>((const T*)da, g.K, g.M, g.K, (uint8_t*)dq, (uint8_t*)dsa, nullptr);
+    e.sa = (const uint8_t*)dsa;
+    e.sw = (const uint8_t*)dsw;
+  } else {
+    dw = m.get(wh.size() * 2);
+    HIPC(hipMemcpy(dw, wh.data(), wh.size() * 2, hipMemcpyHostToDevice));
+  }
+  if (g.bias) {
+    void* db = m.get((size_t)g.N * 4);
+    HIPC(hipMemcpy(db, g.bias, (size_t)g.N * 4, hipMemcpyHostToDevice));
+    e.bias = (const float*)db;
+  }
+  GuardedBuf o0, o1, o2, o3, o4;  // c16 | c32 | q, then k, v, and the MX cache's scales
+  size_t qkb = 0, vb = 0;
+  e.ldc = g.ldc;
+  e.c_bstride = g.c_bstride;
+  if (g.epi == mwx::EPI_GELU) {
+    e.c16 = (uint16_t*)o0.make(m, (size_t)g.c_len * 2, g.c16) + g.c_off;
+    e.gelu_tab = g.use_table ? ctx->c.gelu_tab : nullptr;
+  } else if (g.epi == mwx::EPI_RES || g.epi == mwx::EPI_CONV2) {
+    e.c32 = (float*)o0.make(m, (size_t)g.c_len * 4, g.c32) + g.c_off;
+    if (g.epi == mwx::EPI_RES) {
+      e.r32 = e.c32;
+    } else {
+      void* dp = m.get((size_t)g.M * g.ldc * 4);
+      HIPC(hipMemcpy(dp, g.pe, (size_t)g.M * g.ldc * 4, hipMemcpyHostToDevice));
+      e.pe = (const float*)dp;
+    }
+  } else {
+    const int nb = g.M / g.L;
+    e.L = g.L;
+    e.H = g.H;
+    e.d = g.d;
+    if (g.epi == mwx::EPI_ENC_QKV) {
+      qkb = (size_t)nb * g.H * g.L * 64 * 2;
+      vb = (size_t)nb * g.H * 64 * g.ldv * 2;
+      e.ldv = g.ldv;
+      e.q = (_Float16*)o0.make(m, qkb, g.q);
+    } else {
+      qkb = vb = (size_t)(g.N / (2 * g.d)) * g.ncap * g.H * g.lcap * 64 * 2;
+      e.lcap = g.lcap;
+      e.ncap = g.ncap;
+      e.kscale = g.kscale;
+      void* ds = m.get((size_t)nb * 4);
+      HIPC(hipMemcpy(ds, g.slot, (size_t)nb * 4, hipMemcpyHostToDevice));
+      e.slot = (const int*)ds;
+      if (g.kv8) {  // codes: one byte per element; two scales per row of 64
+        qkb = vb = qkb / 2;
+        e.ks8 = (uint8_t*)o3.make(m, qkb / 32, g.ks8);
+        e.vs8 = (uint8_t*)o4.make(m, qkb / 32, g.vs8);
+      }
+    }
+    e.k = (_Float16*)o1.make(m, qkb, g.kv8 ? (const void*)g.k8 : (const void*)g.k);
+    e.v = (_Float16*)o2.make(m, vb, g.kv8 ? (const void*)g.v8 : (const void*)g.v);
+  }
+  if (g.mx)
+    mwx::gemm_mx<T>(g.epi, (const uint8_t*)dq, g.K, 0, (const uint8_t*)dw, g.K, g.M, g.N, g.K, 1,
+                    e, nullptr);
+  else
+    mwx::gemm<T>(g.epi, g.out16 != 0, (const T*)da, g.lda, g.a_bstride, (const T*)dw, g.K, g.M,
+                 g.N, g.K, g.batch, e, nullptr);
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  bool ok = true;
+  if (g.epi == mwx::EPI_GELU) {
+    ok = o0.take(g.c16);
+  } else if (g.epi == mwx::EPI_RES || g.epi == mwx::EPI_CONV2) {
+    ok = o0.take(g.c32);
+  } else {
+    if (g.epi == mwx::EPI_ENC_QKV) ok = o0.take(g.q);
+    ok = o1.take(g.kv8 ? (void*)g.k8 : (void*)g.k) && ok;
+    ok = o2.take(g.kv8 ? (void*)g.v8 : (void*)g.v) && ok;
+    if (g.kv8) {
+      ok = o3.take(g.ks8) && ok;
+      ok = o4.take(g.vs8) && ok;
+    }
+  }
+  return ok ? 0 : -3;
+}
+
+extern "C" int mwx_test_gemm_enc(struct mwx_context* ctx, const struct mwx_test_gemm_enc_args* gp) {
+  if (!ctx || !gp) return -1;
+  const mwx_test_gemm_enc_args& g = *gp;
+  if (!g.a || !g.w) return -1;
+  if (g.M < 1 || g.M > 4096 || g.N < 64 || g.N > 2048 || g.N % 64 || g.K < 64 || g.K > 5120 ||
+      g.K % 64 || g.batch < 1 || g.batch > 8)
+    return -1;
+  // 16-byte LDS-DMA reads of A: rows and batches start on 8 elements
+  if (g.lda < 8 || g.lda % 8 || g.a_bstride < 0 || g.a_bstride % 8) return -1;
+  if ((long)(g.batch - 1) * g.a_bstride + (long)(g.M - 1) * g.lda + g.K > g.a_len) return -1;
+  if (g.mx && (g.K % 128 || g.lda != g.K || g.batch != 1 || g.epi == mwx::EPI_CONV2 || g.out16))
+    return -1;
+  if (g.kv8 && g.epi != mwx::EPI_CROSS_KV) return -1;
+  const bool flat = g.epi == mwx::EPI_GELU || g.epi == mwx::EPI_RES || g.epi == mwx::EPI_CONV2;
+  if (flat) {
+    // 16-byte stores (8 16-bit words / 4 floats; 8 covers both)
+    if (g.ldc < g.N || g.ldc % 8 || g.c_off < 0 || g.c_off % 8 || g.c_bstride < 0 ||
+        g.c_bstride % 8)
+      return -1;
+    const long span = (long)(g.M - 1) * g.ldc + g.N;
+    if (g.batch > 1 && g.c_bstride < span) return -1;  // batches may not overlap
+    if (g.c_off + (long)(g.batch - 1) * g.c_bstride + span > g.c_len) return -1;
+    if (g.epi == mwx::EPI_GELU ? !g.c16 : !g.c32) return -1;
+    if (g.epi != mwx::EPI_RES && !g.bias) return -1;
+    if (g.epi == mwx::EPI_CONV2 && !g.pe) return -1;
+  } else if (g.epi == mwx::EPI_ENC_QKV || g.epi == mwx::EPI_CROSS_KV) {
+    if (g.batch != 1 || !g.bias) return -1;
+    if (g.kv8 ? (!g.k8 || !g.v8 || !g.ks8 || !g.vs8) : (!g.k || !g.v)) return -1;
+    if (g.d < 64 || g.d % 64 || g.H * 64 != g.d || g.L < 1 || g.M % g.L) return -1;
+    if (g.epi == mwx::EPI_ENC_QKV) {
+      // the 8-byte V^T stores hold 4 consecutive t of one clip
+      if (!g.q || g.N != 3 * g.d || g.L % 4 || g.ldv < g.L || g.ldv % 4) return -1;
+    } else {
+      if (g.N % (2 * g.d) || !g.slot || g.lcap < g.L || g.lcap > 1536 || g.ncap < 1 ||
+          g.ncap > 64)
+        return -1;
+      const int nb = g.M / g.L;
+      uint64_t seen = 0;
+      for (int b = 0; b < nb; ++b) {
+        if (g.slot[b] < 0 || g.slot[b] >= g.ncap || (seen >> g.slot[b] & 1)) return -1;
+        seen |= 1ull << g.slot[b];
+      }
+    }
+  } else {
+    return -1;
+  }
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    if (g.bf16) return test_gemm_enc_impl<__bf16>(ctx, g);
+    return test_gemm_enc_impl<_Float16>(ctx, g);
+  } catch (...) {
+    return -2;
+  }
+}
+
+template <typename T>
+static int test_layer_norm_impl(int dec, int M, int N, float* x, const float* w, const float* b,
+                                const int* active, const float* P, int KS, const float* pbias,
+                                const float* te, const float* pe, const int* tok, const int* pos,
+                                int n_tok, int n_pos, float* y) {
+  const bool bf = std::is_same<T, __bf16>::value;
+  const size_t rb = (size_t)N * 4, xb = (size_t)M * rb;
+  const size_t yrows = dec ? (size_t)(M + 63) / 64 * 64 : (size_t)M;
+  DevScratch m;
+  auto up = [&](const void* src, size_t bytes) -> void* {
+    if (!src) return nullptr;
+    void* d = m.get(bytes);
+    HIPC(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+    return d;
+  };
+  GuardedBuf xg, yg;
+  float* dx = (float*)xg.make(m, xb, x);
+  T* dy = (T*)yg.make(m, yrows * N * 2, nullptr);
+  const float* dw = (const float*)up(w, rb);
+  const float* db = (const float*)up(b, rb);
+  const int* dact = (const int*)up(active, (size_t)M * 4);
+  const float* dP = (const float*)up(P, P ? (size_t)KS * xb : 0);
+  const float* dpb = (const float*)up(pbias, rb);
+  if (!dec) {
+    mwx::layer_norm<T>(dx, dw, db, dy, M, N, dact, nullptr, dP, KS, dpb);
+  } else {
+    mwx::EmbedIn<T> emb;
+    if (te) {
+      std::vector<uint16_t> th((size_t)n_tok * N);
+      for (size_t i = 0; i < th.size(); ++i)
+        th[i] = bf ? mwx::f32_to_bf16(te[i]) : mwx::f32_to_f16(te[i]);
+      emb.te = (const T*)up(th.data(), th.size() * 2);
+      emb.pe = (const float*)up(pe, (size_t)n_pos * rb);
+      emb.tok = (const int*)up(tok, (size_t)M * 4);
+      emb.pos = (const int*)up(pos, (size_t)M * 4);
+      emb.n_tok = n_tok;
+      emb.n_pos = n_pos;
+    }
+    mwx::layer_norm_dec<T>(dx, dw, db, dy, M, N, dact, nullptr, dP, KS, dpb, emb);
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  std::vector<uint16_t> yh(yrows * N);
+  if (!yg.take(yh.data()) || !xg.take(x)) return -3;
+  for (int r = 0; r < M; ++r)
+    for (int c = 0; c < N; ++c) {
+      const uint16_t v = yh[dec ? (size_t)mwx::pack_index(r, c, N) : (size_t)r * N + c];
+      y[(size_t)r * N + c] = bf ? mwx::bf16_to_f32(v) : mwx::f16_to_f32(v);
+    }
+  return 0;
+}
+
+extern "C" int mwx_test_layer_norm(struct mwx_context* ctx, int bf16, int dec, int M, int N,
+                                   float* x, const float* w, const float* b, const int* active,
+                                   const float* P, int KS, const float* pbias, const float* te,
+                                   const float* pe, const int* tok, const int* pos, int n_tok,
+                                   int n_pos, float* y) {
+  if (!ctx || !x || !w || !b || !y || M < 1 || M > 1024 || N < 1) return -1;
+  if (P && (KS < 1 || KS > 8 || !pbias)) return -1;
+  if (te && (!dec || !pe || !tok || !pos || n_tok < 1 || n_pos < 1 || n_tok > 4096 ||
+             n_pos > 4096))
+    return -1;
+  // layer_norm launches nothing for N > 2048; the decode kernel owns 8
+  // elements per thread and writes pack_index tiles (32 deep)
+  if (N > 2048 || (dec && N % 32)) return -4;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    if (bf16)
+      return test_layer_norm_impl<__bf16>(dec, M, N, x, w, b, active, P, KS, pbias, te, pe, tok,
+                                          pos, n_tok, n_pos, y);
+    return test_layer_norm_impl<_Float16>(dec, M, N, x, w, b, active, P, KS, pbias, te, pe, tok,
+                                          pos, n_tok, n_pos, y);
+  } catch (...) {
+    return -2;
+  }
+}
+
+extern "C" int mwx_test_gelu_table_size(void) { return mwx::GELU_TAB_N; }
+
+extern "C" int mwx_test_gelu_table(struct mwx_context* ctx, uint16_t* out) {
+  if (!ctx || !out || !ctx->c.gelu_tab) return -1;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    HIPC(hipMemcpy(out, ctx->c.gelu_tab, (size_t)mwx::GELU_TAB_N * 2, hipMemcpyDeviceToHost));
+    return 0;
+  } catch (...) {
+    return -2;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // DTW token timestamps: the three kernels on given data, and a state's passes
 // ---------------------------------------------------------------------------
 extern "C" int mwx_test_align_probs(struct mwx_context* ctx, int mx, int R, int H, int KS,

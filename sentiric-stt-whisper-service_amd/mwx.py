@@ -134,6 +134,26 @@ class ProsodyParams(C.Structure):
                 ("min_pitch", C.c_float), ("max_pitch", C.c_float)]
 
 
+# GEMM epilogues (csrc/kernels.h enum Epi) that mwx_test_gemm_enc serves
+EPI_ENC_QKV, EPI_GELU, EPI_RES, EPI_CONV2, EPI_CROSS_KV = 0, 1, 2, 3, 5
+
+
+class TestGemmEncArgs(C.Structure):
+    """mwx_test_gemm_enc_args (include/mwx_test.h)."""
+    __test__ = False
+    _fields_ = ([(n, C.c_int) for n in ("bf16", "epi", "out16", "use_table", "mx", "kv8", "M", "N",
+                                        "K", "batch")] +
+                [(n, C.c_long) for n in ("lda", "a_bstride", "a_len", "ldc", "c_bstride", "c_off",
+                                         "c_len")] +
+                [(n, C.c_int) for n in ("L", "H", "d", "ldv", "lcap", "ncap")] +
+                [("kscale", C.c_float)] +
+                [(n, C.POINTER(C.c_float)) for n in ("a", "w", "bias", "pe")] +
+                [("slot", C.POINTER(C.c_int)), ("c16", C.POINTER(C.c_uint16)),
+                 ("c32", C.POINTER(C.c_float))] +
+                [(n, C.POINTER(C.c_uint16)) for n in ("q", "k", "v")] +
+                [(n, C.POINTER(C.c_uint8)) for n in ("k8", "v8", "ks8", "vs8")])
+
+
 class Prosody(C.Structure):
     """mwx_prosody = AffectiveTags (src/prosody_extractor.h:6-18)."""
     _fields_ = [(n, C.c_float) for n in ("pitch_mean", "pitch_std", "energy_mean", "energy_std",
@@ -1070,6 +1090,150 @@ class Context:
         if rc != 0:
             raise RuntimeError(f"mwx_test_gemm_dec failed ({rc})")
         return out[:ks.value].copy() if mode == 0 else out[0]
+
+    @staticmethod
+    def _hook_rc(name: str, rc: int):
+        if rc == -1:
+            raise ValueError(f"{name} refused its arguments")
+        if rc == -4:
+            raise NotImplementedError(f"{name}: shape not served by the kernel family")
+        if rc != 0:
+            raise RuntimeError(f"{name} failed ({rc})")
+
+    def test_enc_attn(self, q: np.ndarray, k: np.ndarray, vt: np.ndarray, *, bf16: bool,
+                      scale: float, lens=None) -> np.ndarray:
+        """mwx_test_enc_attn: q, k [B][H][L][64] and vt [B][H][64][Lp] float16
+        (Lp = L rounded up to 8, pad columns included). Returns o [B*L][H*64]
+        f32; a word the launch did not write is NaN."""
+        assert q.dtype == np.float16 and k.dtype == np.float16 and vt.dtype == np.float16
+        B, H, L, _ = q.shape
+        assert q.shape == (B, H, L, 64) and k.shape == q.shape
+        assert vt.shape == (B, H, 64, (L + 7) & ~7), vt.shape
+        q, k, vt = (np.ascontiguousarray(a).view(np.uint16) for a in (q, k, vt))
+        ip, u16p = C.POINTER(C.c_int), C.POINTER(C.c_uint16)
+        if lens is not None:
+            lens = np.ascontiguousarray(lens, dtype=np.int32)
+            assert lens.shape == (B,)
+        o = np.empty((B * L, H * 64), np.float32)
+        fn = lib().mwx_test_enc_attn
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] + [C.c_int] * 4 + [ip, C.c_float, u16p, u16p, u16p,
+                                                      C.POINTER(C.c_float)]
+        rc = fn(self.ctx, int(bf16), B, H, L, ip() if lens is None else lens.ctypes.data_as(ip),
+                scale, q.ctypes.data_as(u16p), k.ctypes.data_as(u16p), vt.ctypes.data_as(u16p),
+                fptr(o))
+        self._hook_rc("mwx_test_enc_attn", rc)
+        return o
+
+    def test_gemm_enc(self, epi: int, a: np.ndarray, w: np.ndarray, *, bf16: bool, M: int,
+                      lda: Optional[int] = None, a_bstride: int = 0, batch: int = 1, bias=None,
+                      pe=None, c16=None, c32=None, ldc: Optional[int] = None, c_bstride: int = 0,
+                      c_off: int = 0, out16: bool = False, use_table: bool = True, L: int = 0,
+                      H: int = 0, d: int = 0, ldv: int = 0, lcap: int = 0, ncap: int = 0,
+                      slot=None, kscale: float = 1.0, q=None, k=None, v=None, mx: bool = False,
+                      kv8=None):
+        """mwx_test_gemm_enc (include/mwx_test.h): a = any f32 array (read flat
+        through lda / a_bstride), w [N][K]. The output arrays (c16 uint16 / c32
+        float32 flat, q / k / v uint16) are copied, run through the launch and
+        returned: c16 | c32 | (q, k, v) | (k, v). kv8 = (k8, v8, ks8, vs8) uint8:
+        the MX-fp8 cross cache instead of k / v, returned as such a tuple."""
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        N, K = w.shape
+        f32 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float32)
+        u16 = lambda x: None if x is None else np.array(x, dtype=np.uint16, order="C")
+        bias, pe = f32(bias), f32(pe)
+        c16, q, k, v = u16(c16), u16(q), u16(k), u16(v)
+        c32 = None if c32 is None else np.array(c32, dtype=np.float32, order="C")
+        slot = None if slot is None else np.ascontiguousarray(slot, dtype=np.int32)
+        g = TestGemmEncArgs()
+        g.bf16, g.epi, g.out16, g.use_table = int(bf16), epi, int(out16), int(use_table)
+        g.mx, g.kv8 = int(mx), int(kv8 is not None)
+        if kv8 is not None:
+            kv8 = tuple(np.array(x, dtype=np.uint8, order="C") for x in kv8)
+            assert d > 0 and kv8[0].size == kv8[1].size == (N // (2 * d)) * ncap * H * lcap * 64
+            assert kv8[2].size == kv8[3].size == kv8[0].size // 32
+            g.k8, g.v8, g.ks8, g.vs8 = (x.ctypes.data_as(C.POINTER(C.c_uint8)) for x in kv8)
+        g.M, g.N, g.K, g.batch = M, N, K, batch
+        g.lda, g.a_bstride, g.a_len = K if lda is None else lda, a_bstride, a.size
+        cbuf = c16 if c16 is not None else c32
+        g.ldc, g.c_bstride, g.c_off = N if ldc is None else ldc, c_bstride, c_off
+        g.c_len = 0 if cbuf is None else cbuf.size
+        g.L, g.H, g.d, g.ldv, g.lcap, g.ncap, g.kscale = L, H, d, ldv, lcap, ncap, kscale
+        if pe is not None:
+            assert pe.shape == (M, g.ldc), pe.shape
+        if bias is not None:
+            assert bias.shape == (N,)
+        if slot is not None:
+            assert L > 0 and slot.shape == (M // L,)
+        if epi == EPI_ENC_QKV and L > 0 and H > 0 and ldv > 0 and q is not None:
+            assert q.size == k.size == (M // L) * H * L * 64 and v.size == (M // L) * H * 64 * ldv
+        if epi == EPI_CROSS_KV and d > 0 and k is not None:
+            assert k.size == v.size == (N // (2 * d)) * ncap * H * lcap * 64
+        ptr = lambda x, t: C.POINTER(t)() if x is None else x.ctypes.data_as(C.POINTER(t))
+        g.a, g.w = ptr(a, C.c_float), ptr(w, C.c_float)
+        g.bias, g.pe, g.slot = ptr(bias, C.c_float), ptr(pe, C.c_float), ptr(slot, C.c_int)
+        g.c16, g.c32 = ptr(c16, C.c_uint16), ptr(c32, C.c_float)
+        g.q, g.k, g.v = ptr(q, C.c_uint16), ptr(k, C.c_uint16), ptr(v, C.c_uint16)
+        fn = lib().mwx_test_gemm_enc
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(TestGemmEncArgs)]
+        self._hook_rc("mwx_test_gemm_enc", fn(self.ctx, C.byref(g)))
+        if epi == EPI_GELU:
+            return c16
+        if epi in (EPI_RES, EPI_CONV2):
+            return c32
+        if kv8 is not None:
+            return kv8
+        return (q, k, v) if epi == EPI_ENC_QKV else (k, v)
+
+    def test_layer_norm(self, x: np.ndarray, w: np.ndarray, b: np.ndarray, *, bf16: bool,
+                        dec: bool = False, active=None, P=None, pbias=None, te=None, pe=None,
+                        tok=None, pos=None):
+        """mwx_test_layer_norm: x [M][N] f32 (not modified). Returns (y [M][N]
+        f32, x after the launch); a row the launch did not write is NaN in y."""
+        x = np.array(x, dtype=np.float32, order="C")
+        M, N = x.shape
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        w, b, P, pbias, te, pe = (f32(a) for a in (w, b, P, pbias, te, pe))
+        active, tok, pos = (i32(a) for a in (active, tok, pos))
+        assert w.shape == (N,) and b.shape == (N,)
+        KS = 0
+        if P is not None:
+            KS = P.shape[0]
+            assert P.shape == (KS, M, N) and pbias.shape == (N,)
+        for a in (active, tok, pos):
+            assert a is None or a.shape == (M,)
+        n_tok = n_pos = 0
+        if te is not None:
+            n_tok, n_pos = te.shape[0], pe.shape[0]
+            assert te.shape == (n_tok, N) and pe.shape == (n_pos, N)
+        fpp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+        fp = lambda a: fpp() if a is None else fptr(a)
+        ipt = lambda a: ip() if a is None else a.ctypes.data_as(ip)
+        y = np.empty((M, N), np.float32)
+        fn = lib().mwx_test_layer_norm
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] + [C.c_int] * 4 + [fpp, fpp, fpp, ip, fpp, C.c_int, fpp, fpp,
+                                                      fpp, ip, ip, C.c_int, C.c_int, fpp]
+        rc = fn(self.ctx, int(bf16), int(dec), M, N, fptr(x), fptr(w), fptr(b), ipt(active), fp(P),
+                KS, fp(pbias), fp(te), fp(pe), ipt(tok), ipt(pos), n_tok, n_pos, fptr(y))
+        self._hook_rc("mwx_test_layer_norm", rc)
+        return y, x
+
+    def test_gelu_table(self) -> np.ndarray:
+        """The device-built f16 GELU table as uint16 bits (index: see
+        mwx_test_gelu_table)."""
+        L = lib()
+        L.mwx_test_gelu_table_size.restype = C.c_int
+        L.mwx_test_gelu_table_size.argtypes = []
+        tab = np.empty(L.mwx_test_gelu_table_size(), np.uint16)
+        L.mwx_test_gelu_table.restype = C.c_int
+        L.mwx_test_gelu_table.argtypes = [C.c_void_p, C.POINTER(C.c_uint16)]
+        self._hook_rc("mwx_test_gelu_table",
+                      L.mwx_test_gelu_table(self.ctx, tab.ctypes.data_as(C.POINTER(C.c_uint16))))
+        return tab
 
     def test_decode_last(self, tokens: Sequence[int], out: Optional[np.ndarray] = None,
                          state_index: int = 0) -> np.ndarray:
