@@ -590,6 +590,58 @@ int mwx_write_synthetic_vad_model(const char* path, uint64_t seed);
  * K types) fails with -8, as ggml's quantizer does. Returns 0 on success. */
 int mwx_model_quantize(const char* in_path, const char* out_path, int type);
 
+/* --- chunked long-form transcription ------------------------------------------
+ * One long recording as a batch (the rule is written out in
+ * INTEGRATION.md "Chunked long-form transcription"): the clip's pieces are
+ * packed, in order, into chunks of at most chunk_s seconds of compacted audio
+ * (csrc/k_vad.hip, vad_chunks_kernel), a piece longer than that being a chunk
+ * of its own, and every chunk is decoded as an independent batch entry. This
+ * project's definition: parity with faster-whisper's or WhisperX's batched
+ * pipelines is not claimed. */
+
+/* As mwx_vad_trim_batch, plus a chunk plan (rule D10). chunk_s in [1, 30];
+ * anything else, NaN included, is refused (NULL, logged). Segments, pieces and
+ * the compacted PCM are those of mwx_vad_trim_batch. */
+struct mwx_vad_trimmed* mwx_vad_trim_batch_chunked(struct mwx_vad_context* vctx,
+                                                   struct mwx_vad_params params, float chunk_s,
+                                                   const float* const* samples,
+                                                   const int* n_samples, int n_clips);
+/* The chunks of a clip. An object made by mwx_vad_trim_batch reports one chunk
+ * per clip that has segments: the whole compacted clip. */
+int mwx_vad_trimmed_n_chunks(const struct mwx_vad_trimmed* t, int clip);
+/* Chunk j: its first segment and segment count, its start and length in
+ * samples of the compacted clip (the gap zeros after its last piece are not
+ * part of it). 0, or < 0 out of range. Outputs are nullable. */
+int mwx_vad_trimmed_chunk(const struct mwx_vad_trimmed* t, int clip, int j, int* first_segment,
+                          int* n_segments, int64_t* start, int64_t* len);
+/* As mwx_vad_trimmed_map_time for a time counted from the start of chunk j. A
+ * value past the chunk's end maps to the end of its last piece. */
+int64_t mwx_vad_trimmed_chunk_map_time(const struct mwx_vad_trimmed* t, int clip, int j,
+                                       int64_t t_cs, bool is_end);
+/* Device time of the last mwx_vad_trim_batch_chunked's vad_chunks_kernel in
+ * milliseconds. 0 on success, -1 if no plan was made. */
+int mwx_vad_last_chunk_kernel_ms(struct mwx_vad_context* vctx, float* chunks_ms);
+
+/* Batch entry b = clip clip_index[b] of trimmed[b]; every chunk of every entry is one
+ * entry of an internal mwx_full_batch run, at most max_batch (>= 1) per run, in
+ * (entry, chunk) order. Entry 0 of every run works on states[0]; the others on
+ * scratch states that states[0] owns (created on first use, at most
+ * max_batch - 1, freed with it). states[b] ends with the segments of its
+ * clip's chunks in chunk order, every segment and token time on the caller's
+ * timeline (mwx_vad_trimmed_chunk_map_time), and its first chunk's language
+ * id; a clip without chunks ends with 0 segments. Every chunk is an
+ * independent clip to the engine: the prompt parameters apply to each one and
+ * language = "auto" detects per chunk; a chunk shorter than 0.1 s decodes to
+ * nothing, as a clip that short does. The result does not depend on
+ * max_batch. params.offset_ms and params.duration_ms must be 0 (-1, logged).
+ * On an error or an abort (polled between runs too) the code is returned and
+ * every state of the call holds 0 segments. For an object made by
+ * mwx_vad_trim_batch this is mwx_full_batch_trimmed. */
+int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* states,
+                           struct mwx_full_params params,
+                           const struct mwx_vad_trimmed* const* trimmed, const int* clip_index,
+                           int n_clips, int max_batch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -361,6 +361,16 @@ int mwx_test_dtw_last(struct mwx_state* state, int pass, int* dims, int64_t* see
 int mwx_test_dtw_align(struct mwx_context* ctx, struct mwx_state* state, const int* tokens, int n,
                        int pos0, int n_cols);
 
+/* vad_segments_kernel, then vad_chunks_kernel on
+ * caller-supplied probabilities, laid out as for mwx_test_vad_segments; clip b
+ * is packed with its own cap caps[b] >= 1 in samples. Out: n_chunks[b] and its
+ * chunks as (first piece, n pieces, start, len) at chunks + 4 * out_offset[b];
+ * room for as many entries as the clip has 512-sample chunks. Returns 0 or < 0. */
+int mwx_test_vad_chunks(struct mwx_vad_context* vctx, const struct mwx_vad_params* params,
+                        const int64_t* caps, const float* probs, const int* probs_offset,
+                        const int* n_samples, int n_clips, int* n_chunks, int64_t* chunks,
+                        const int* out_offset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1630,6 +1630,8 @@ struct mwx_state* mwx_init_state(struct mwx_context* ctx) {
 
 void mwx_free_state(struct mwx_state* state) {
   if (!state) return;
+  for (mwx_state* sc : state->scratch) mwx_free_state(sc);
+  state->scratch.clear();
   std::lock_guard<std::recursive_mutex> lock(mwx::capture_mutex());
   State& S = state->s;
   if (S.ctx) (void)hipSetDevice(S.ctx->device);
@@ -1807,6 +1809,107 @@ int mwx_full_batch_trimmed(struct mwx_context* ctx, struct mwx_state* const* sta
         if (td.t_dtw >= 0) td.t_dtw = mwx::vad_map_time(*run_clips[r], td.t_dtw, false);
       }
     }
+  return 0;
+}
+
+// A clip's chunks (vad.cpp, mwx_vad_trim_batch_chunked; DESIGN.md D10) as batch
+// entries: the chunks of all entries, in (entry, chunk) order, go through
+// full_batch_any in runs of at most max_batch, entry 0 of a run on states[0]
+// and the rest on its scratch states; each run's segments are moved out, their
+// times mapped by the chunk's map, and appended to the clip they belong to.
+int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* states,
+                           struct mwx_full_params params,
+                           const struct mwx_vad_trimmed* const* trimmed, const int* clip_index,
+                           int n_clips, int max_batch) {
+  if (!ctx || !states || !trimmed || !clip_index || n_clips <= 0 || max_batch < 1) return -1;
+  struct Job {
+    int entry;
+    int64_t chunk;
+    const mwx_vad_trimmed::Clip* clip;
+    const float* pcm;
+    int len;
+  };
+  std::vector<Job> jobs;
+  for (int b = 0; b < n_clips; ++b)  // (an error below leaves every state with 0 segments)
+    if (states[b]) states[b]->s.result_all.clear();
+  for (int b = 0; b < n_clips; ++b) {
+    const mwx_vad_trimmed* t = trimmed[b];
+    if (!states[b] || !t || clip_index[b] < 0 || (size_t)clip_index[b] >= t->clips.size())
+      return -1;
+    if (t->device != ctx->c.device) {
+      MWX_LOG_ERROR("mwx_full_batch_chunked: trimmed audio of device %d, context on device %d\n",
+                    t->device, ctx->c.device);
+      return -1;
+    }
+    if (t->clips[clip_index[b]].n_compact > 0x7fffffffLL) return -1;
+  }
+  if (params.offset_ms != 0 || params.duration_ms != 0) {
+    MWX_LOG_ERROR("mwx_full_batch_chunked: offset_ms and duration_ms must be 0\n");
+    return -1;
+  }
+  for (int b = 0; b < n_clips; ++b) {
+    const mwx_vad_trimmed::Clip& c = trimmed[b]->clips[clip_index[b]];
+    if (c.seg.empty() || c.n_compact <= 0) continue;
+    for (int64_t j = 0; 2 * j + 1 < (int64_t)c.chunk.size(); ++j) {
+      int64_t first, n, start, len;
+      if (!mwx::vad_chunk_span(c, j, first, n, start, len) || start < 0 || len < 0 ||
+          start + len > c.n_compact)
+        return -1;
+      jobs.push_back({b, j, &c, trimmed[b]->d_pcm + c.off + start, (int)len});
+    }
+  }
+  if (jobs.empty()) return 0;
+  mwx_state* s0 = states[0];
+  const size_t width = std::min((size_t)max_batch, jobs.size());
+  while (s0->scratch.size() + 1 < width) {
+    mwx_state* sc = mwx_init_state(ctx);
+    if (!sc) return -1;
+    s0->scratch.push_back(sc);
+  }
+  std::vector<mwx_state*> run_states{s0};
+  run_states.insert(run_states.end(), s0->scratch.begin(), s0->scratch.begin() + (width - 1));
+  std::vector<std::vector<mwx::Segment>> acc((size_t)n_clips);
+  std::vector<int> lang((size_t)n_clips, -1);
+  int rc = 0;
+  for (size_t r0 = 0; r0 < jobs.size() && rc == 0; r0 += width) {
+    const size_t n = std::min(width, jobs.size() - r0);
+    if (r0 > 0 && mwx::aborted(params)) {
+      rc = -9;
+      break;
+    }
+    std::vector<const void*> ptrs;
+    std::vector<int> lens;
+    for (size_t i = 0; i < n; ++i) {
+      ptrs.push_back(jobs[r0 + i].pcm);
+      lens.push_back(jobs[r0 + i].len);
+    }
+    rc = full_batch_any(ctx, run_states.data(), params, ptrs.data(), lens.data(), (int)n, false);
+    if (rc != 0) break;
+    for (size_t i = 0; i < n; ++i) {
+      const Job& jb = jobs[r0 + i];
+      mwx::State& rs = run_states[i]->s;
+      for (auto& sg : rs.result_all) {
+        sg.t0 = mwx::vad_chunk_map_time(*jb.clip, jb.chunk, sg.t0, false);
+        sg.t1 = mwx::vad_chunk_map_time(*jb.clip, jb.chunk, sg.t1, true);
+        for (auto& td : sg.tokens) {
+          td.t0 = mwx::vad_chunk_map_time(*jb.clip, jb.chunk, td.t0, false);
+          td.t1 = mwx::vad_chunk_map_time(*jb.clip, jb.chunk, td.t1, true);
+          if (td.t_dtw >= 0) td.t_dtw = mwx::vad_chunk_map_time(*jb.clip, jb.chunk, td.t_dtw, false);
+        }
+        acc[jb.entry].push_back(std::move(sg));
+      }
+      rs.result_all.clear();
+      if (jb.chunk == 0) lang[jb.entry] = rs.lang_id;
+    }
+  }
+  for (mwx_state* rs : run_states) rs->s.result_all.clear();
+  for (int b = 0; b < n_clips; ++b) states[b]->s.result_all.clear();
+  if (rc != 0) return rc;
+  for (int b = 0; b < n_clips; ++b) {
+    if (lang[b] < 0) continue;
+    states[b]->s.result_all = std::move(acc[b]);
+    states[b]->s.lang_id = lang[b];
+  }
   return 0;
 }
 

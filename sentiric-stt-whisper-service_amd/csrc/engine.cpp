@@ -1788,6 +1788,9 @@ struct mwx_context {
 };
 struct mwx_state {
   mwx::State s;
+  // mwx_full_batch_chunked: the states of a run's entries 1 .. max_batch - 1,
+  // created on first use and freed with this state
+  std::vector<mwx_state*> scratch;
 };
 
 // The decode-loop / window logic lives in driver.cpp (same TU via include to

@@ -368,6 +368,49 @@ __global__ __launch_bounds__(64) void vad_segments_kernel(
   }
 }
 
+// ---- chunk plan ---------------------------------------------------------------
+// One wave per clip, over the piece table vad_segments_kernel left (DESIGN.md
+// D10). The walk over chunk starts is serial and wave-uniform; the search for
+// the first piece that does not fit is one piece per lane, 64 pieces a round:
+// piece k > a fits chunk a while dst_k + len_k - dst_a <= L. Lane 0 stores.
+__global__ __launch_bounds__(64) void vad_chunks_kernel(
+    const int* __restrict__ chunk_off, int n_clips, const long long* __restrict__ tables,
+    const long long* __restrict__ caps, int cap_stride, long long* __restrict__ ctabs) {
+  const int b = blockIdx.x;
+  if (b >= n_clips) return;
+  const int lane = threadIdx.x;
+  const int off = chunk_off[b];
+  const int cap = chunk_off[b + 1] - off + 1;
+  const long long* __restrict__ T = tables + vad_table_off(off, b);
+  const int m = (int)max(0LL, min(T[0], (long long)cap));
+  const long long* __restrict__ pc = T + 2 + 2LL * cap;
+  const long long L = caps[(size_t)b * cap_stride];
+  long long* __restrict__ X = ctabs + vad_chunk_table_off(off, b);
+  int nc = 0;
+  int a = 0;
+  while (a < m) {
+    const long long c0 = pc[3 * a + 2];
+    int nxt = m;
+    for (int base = a + 1; base < m; base += 64) {
+      const int k = base + lane;
+      const bool over = k < m && pc[3 * k + 2] + pc[3 * k + 1] - c0 > L;
+      const unsigned long long mo = __ballot(over);
+      if (mo != 0) {
+        // the pieces of this round that still fit: those below the first that does not
+        nxt = base + __popcll((mo & (0ULL - mo)) - 1);
+        break;
+      }
+    }
+    if (lane == 0 && nc < cap) {
+      X[1 + 2 * nc] = a;
+      X[2 + 2 * nc] = nxt - a;
+    }
+    ++nc;
+    a = nxt;
+  }
+  if (lane == 0) X[0] = min(nc, cap);
+}
+
 // ---- compaction ---------------------------------------------------------------
 // grid.x = n_clips * tiles (tiles = ceil(max_len / VAD_CP_TILE)); workgroup
 // (clip b, tile x) writes compacted samples [x * VAD_CP_TILE, ...) of clip b
@@ -443,6 +486,12 @@ void vad_segments_launch(const float* probs, const int* n_samples, const int* ch
   if (n_clips <= 0) return;
   vad_segments_kernel<<<n_clips, 64, 0, st>>>(probs, n_samples, chunk_off, n_clips, prm,
                                               prm_stride, tables);
+}
+
+void vad_chunks_launch(const int* chunk_off, int n_clips, const long long* tables,
+                       const long long* caps, int cap_stride, long long* ctabs, hipStream_t st) {
+  if (n_clips <= 0) return;
+  vad_chunks_kernel<<<n_clips, 64, 0, st>>>(chunk_off, n_clips, tables, caps, cap_stride, ctabs);
 }
 
 void vad_compact_launch(const float* const* pcm, const int* n_samples, const int* chunk_off,

@@ -555,6 +555,17 @@ __host__ __device__ inline long long vad_table_off(long long chunk_off_b, long l
 void vad_segments_launch(const float* probs, const int* n_samples, const int* chunk_off,
                          int n_clips, const VadSegParams* prm, int prm_stride, long long* tables,
                          hipStream_t st);
+// The chunk plan has a table buffer of its own: clip b's table
+// starts vad_chunk_table_off(chunk_off[b], b) int64 entries into it and holds
+// 1 + 2 cap of them (cap as above: a chunk has at least one piece):
+//   [0] chunk count   [1 ..) the chunks (first piece, n pieces)
+__host__ __device__ inline long long vad_chunk_table_off(long long chunk_off_b, long long b) {
+  return 2 * chunk_off_b + 3 * b;
+}
+// One wave per clip, after vad_segments_launch on the same stream: packs the
+// pieces in `tables` into chunks of at most caps[b * cap_stride] samples.
+void vad_chunks_launch(const int* chunk_off, int n_clips, const long long* tables,
+                       const long long* caps, int cap_stride, long long* ctabs, hipStream_t st);
 // Gathers every clip's pieces (and the gap zeros) into out + out_off[b]
 // (16-byte aligned starts); max_len = the longest compacted length.
 void vad_compact_launch(const float* const* pcm, const int* n_samples, const int* chunk_off,

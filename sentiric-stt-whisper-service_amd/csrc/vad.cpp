@@ -1,6 +1,7 @@
 // Voice-activity detection: the model file (reader and seeded writer), the
 // VAD context and the mwx_vad_* entry points of include/mwx.h, speech segments
-// and silence trimming (mwx_vad_segments_*, mwx_vad_trim_batch) included. The
+// and silence trimming (mwx_vad_segments_*, mwx_vad_trim_batch) and the chunk
+// plan of a long clip (mwx_vad_trim_batch_chunked) included. The
 // kernels are in k_vad.hip; the network, the file layout and the segment rule
 // are written down in INTEGRATION.md ("VAD model", "VAD speech segments").
 #include <hip/hip_runtime.h>
@@ -246,13 +247,13 @@ bool vad_is_device_ptr(const void* p) {
 struct mwx_vad_context {
   int device = 0;
   hipStream_t stream = nullptr;
-  // front end | recurrence | segments, then around the compaction
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool timed = false, timed_trim = false;
+  // front end | recurrence | segments, around the compaction, around the chunk plan
+  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool timed = false, timed_trim = false, timed_chunks = false;
   float* d_weights = nullptr;
   mwx::VadWeights w{};
-  mwx::VBuf d_pcm, d_pre, d_probs, d_meta, d_tab, d_ooff;
-  mwx::PinBuf h_meta, h_probs, h_tab, h_ooff;
+  mwx::VBuf d_pcm, d_pre, d_probs, d_meta, d_tab, d_ooff, d_ctab, d_caps;
+  mwx::PinBuf h_meta, h_probs, h_tab, h_ooff, h_ctab, h_caps;
   std::vector<float> probs;  // mwx_vad_probs
   int probs_n_samples = 0;   // the clip length they belong to
 };
@@ -270,6 +271,10 @@ void vad_destroy(mwx_vad_context* v) {
   v->d_meta.release();
   v->d_tab.release();
   v->d_ooff.release();
+  v->d_ctab.release();
+  v->d_caps.release();
+  v->h_ctab.release();
+  v->h_caps.release();
   v->h_meta.release();
   v->h_probs.release();
   v->h_tab.release();
@@ -423,7 +428,7 @@ void vad_upload_meta(mwx_vad_context* v, const std::vector<const float*>& ptrs,
 int vad_forward(mwx_vad_context* v, const float* const* samples, const int* n_samples, int n_clips,
                 const VadSegParams* prm, int n_prm, VadPass& ps) {
   HIPC(hipSetDevice(v->device));
-  v->timed = v->timed_trim = false;
+  v->timed = v->timed_trim = v->timed_chunks = false;
   std::vector<size_t> stage((size_t)n_clips, 0);
   std::vector<char> on_device((size_t)n_clips, 0);
   size_t stage_floats = 0;
@@ -481,9 +486,13 @@ int vad_run(mwx_vad_context* v, const float* const* samples, const int* n_sample
 
 // vad_segments_kernel over the probabilities in d_probs, then the one copy
 // back: the tables of every clip (kernels.h, vad_table_off) in pinned memory,
-// valid until the context's next call. Synchronizes.
+// valid until the context's next call. Synchronizes. With caps (one cap in
+// samples for all clips, n_caps = 1, or one per clip), vad_chunks_kernel runs
+// behind it and the chunk tables (kernels.h, vad_chunk_table_off) come back in
+// v->h_ctab with the same synchronize.
 const int64_t* vad_segment_tables(mwx_vad_context* v, int n_clips, int prm_stride,
-                                  const VadPass& ps) {
+                                  const VadPass& ps, const int64_t* caps = nullptr,
+                                  int n_caps = 0) {
   static_assert(sizeof(long long) == sizeof(int64_t), "table entries");
   hipStream_t st = v->stream;
   const size_t n_tab = (size_t)vad_table_off(ps.total, n_clips);
@@ -494,8 +503,41 @@ const int64_t* vad_segment_tables(mwx_vad_context* v, int n_clips, int prm_strid
   HIPC(hipEventRecord(v->ev[3], st));
   HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(h_tab, d_tab, n_tab * 8, hipMemcpyDeviceToHost, st));
+  if (n_caps > 0) {
+    const size_t n_ctab = (size_t)vad_chunk_table_off(ps.total, n_clips);
+    long long* d_ctab = (long long*)v->d_ctab.get(n_ctab * 8, st);
+    int64_t* h_ctab = (int64_t*)v->h_ctab.get(n_ctab * 8);
+    long long* d_caps = (long long*)v->d_caps.get((size_t)n_caps * 8, st);
+    int64_t* h_caps = (int64_t*)v->h_caps.get((size_t)n_caps * 8);
+    memcpy(h_caps, caps, (size_t)n_caps * 8);
+    HIPC(hipMemcpyAsync(d_caps, h_caps, (size_t)n_caps * 8, hipMemcpyHostToDevice, st));
+    HIPC(hipEventRecord(v->ev[6], st));
+    vad_chunks_launch(ps.d_off, n_clips, d_tab, d_caps, n_caps > 1 ? 1 : 0, d_ctab, st);
+    HIPC(hipEventRecord(v->ev[7], st));
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(h_ctab, d_ctab, n_ctab * 8, hipMemcpyDeviceToHost, st));
+  }
   HIPC(hipStreamSynchronize(st));
+  v->timed_chunks = n_caps > 0;
   return h_tab;
+}
+
+// Clip b's chunk table -> (first piece, n pieces) pairs; false when the table
+// is not a partition of the clip's m pieces in order.
+bool vad_read_chunk_table(const int64_t* h_ctab, const VadPass& ps, int b, int64_t m,
+                          std::vector<int64_t>& chunk) {
+  const int64_t* X = h_ctab + vad_chunk_table_off(ps.off[b], b);
+  const int64_t cap = ps.off[b + 1] - ps.off[b] + 1;
+  const int64_t nc = X[0];
+  if (nc < 0 || nc > cap) return false;
+  int64_t next = 0;
+  for (int64_t j = 0; j < nc; ++j) {
+    if (X[1 + 2 * j] != next || X[2 + 2 * j] < 1) return false;
+    next += X[2 + 2 * j];
+  }
+  if (next != m) return false;
+  chunk.assign(X + 1, X + 1 + 2 * nc);
+  return true;
 }
 
 // Clip b's table -> segments and pieces; false when the table is not one the
@@ -517,9 +559,10 @@ bool vad_read_table(const int64_t* h_tab, const VadPass& ps, int b, std::vector<
 // prm: one entry per clip.
 int vad_segments_of_probs(mwx_vad_context* v, const VadSegParams* prm, const float* probs,
                           const int* probs_offset, const int* n_samples, int n_clips,
-                          std::vector<mwx_vad_trimmed::Clip>& out) {
+                          std::vector<mwx_vad_trimmed::Clip>& out,
+                          const int64_t* caps = nullptr) {
   HIPC(hipSetDevice(v->device));
-  v->timed = v->timed_trim = false;
+  v->timed = v->timed_trim = v->timed_chunks = false;
   VadPass ps;
   const int rc = vad_chunk_offsets(n_samples, n_clips, ps);
   if (rc != 0) return rc;
@@ -535,29 +578,40 @@ int vad_segments_of_probs(mwx_vad_context* v, const VadSegParams* prm, const flo
     HIPC(hipMemcpyAsync(d_probs, h_probs, (size_t)ps.total * 4, hipMemcpyHostToDevice, st));
   vad_upload_meta(v, std::vector<const float*>((size_t)n_clips, nullptr), n_samples, n_clips, prm,
                   n_clips, ps);
-  const int64_t* h_tab = vad_segment_tables(v, n_clips, 1, ps);
-  for (int b = 0; b < n_clips; ++b)
+  const int64_t* h_tab = vad_segment_tables(v, n_clips, 1, ps, caps, caps ? n_clips : 0);
+  for (int b = 0; b < n_clips; ++b) {
     if (!vad_read_table(h_tab, ps, b, out[b].seg, out[b].piece, out[b].n_compact)) return -5;
+    if (caps && !vad_read_chunk_table((const int64_t*)v->h_ctab.p, ps, b,
+                                      (int64_t)out[b].piece.size() / 3, out[b].chunk))
+      return -5;
+  }
   return 0;
 }
 
 // VAD, segments and compaction of all clips; fills t (whose d_pcm the caller
-// frees, also after an exception).
+// frees, also after an exception). chunk_cap > 0: the chunk plan with that cap
+// in samples; 0: no plan, every clip that has segments is one chunk.
 int vad_trim_run(mwx_vad_context* v, const VadSegParams& prm, const float* const* samples,
-                 const int* n_samples, int n_clips, mwx_vad_trimmed& t) {
+                 const int* n_samples, int n_clips, mwx_vad_trimmed& t, int64_t chunk_cap) {
   t.device = v->device;
   t.clips.assign((size_t)n_clips, mwx_vad_trimmed::Clip());
   VadPass ps;
   const int rc = vad_forward(v, samples, n_samples, n_clips, &prm, 1, ps);
   if (rc != 0 || ps.total == 0) return rc;
   hipStream_t st = v->stream;
-  const int64_t* h_tab = vad_segment_tables(v, n_clips, 0, ps);
+  const int64_t* h_tab = vad_segment_tables(v, n_clips, 0, ps, &chunk_cap, chunk_cap > 0 ? 1 : 0);
   size_t total = 0;
   int64_t max_len = 0;
   int64_t* h_ooff = (int64_t*)v->h_ooff.get((size_t)n_clips * 8);
   for (int b = 0; b < n_clips; ++b) {
     mwx_vad_trimmed::Clip& c = t.clips[b];
     if (!vad_read_table(h_tab, ps, b, c.seg, c.piece, c.n_compact)) return -5;
+    const int64_t m = (int64_t)c.piece.size() / 3;
+    if (chunk_cap > 0) {
+      if (!vad_read_chunk_table((const int64_t*)v->h_ctab.p, ps, b, m, c.chunk)) return -5;
+    } else if (m > 0) {
+      c.chunk = {0, m};
+    }
     c.off = total;
     h_ooff[b] = (int64_t)total;
     total += ((size_t)c.n_compact + 3) / 4 * 4;  // 16-byte aligned clip starts
@@ -734,8 +788,8 @@ float mwx_vad_segments_get_segment_t1(struct mwx_vad_segments* s, int i) {
 }
 void mwx_vad_free_segments(struct mwx_vad_segments* s) { delete s; }
 
-struct mwx_vad_trimmed* mwx_vad_trim_batch(struct mwx_vad_context* vctx,
-                                           struct mwx_vad_params params,
+static mwx_vad_trimmed* vad_trim_batch_any(struct mwx_vad_context* vctx,
+                                           struct mwx_vad_params params, int64_t chunk_cap,
                                            const float* const* samples, const int* n_samples,
                                            int n_clips) {
   if (!vctx || n_clips < 0 || (n_clips > 0 && (!samples || !n_samples))) return nullptr;
@@ -746,7 +800,7 @@ struct mwx_vad_trimmed* mwx_vad_trim_batch(struct mwx_vad_context* vctx,
   if (n_clips == 0) return t;
   int rc = -4;
   try {
-    rc = mwx::vad_trim_run(vctx, prm, samples, n_samples, n_clips, *t);
+    rc = mwx::vad_trim_run(vctx, prm, samples, n_samples, n_clips, *t, chunk_cap);
   } catch (const std::exception&) {
   }
   if (rc != 0) {
@@ -755,6 +809,25 @@ struct mwx_vad_trimmed* mwx_vad_trim_batch(struct mwx_vad_context* vctx,
     return nullptr;
   }
   return t;
+}
+
+struct mwx_vad_trimmed* mwx_vad_trim_batch(struct mwx_vad_context* vctx,
+                                           struct mwx_vad_params params,
+                                           const float* const* samples, const int* n_samples,
+                                           int n_clips) {
+  return vad_trim_batch_any(vctx, params, 0, samples, n_samples, n_clips);
+}
+
+struct mwx_vad_trimmed* mwx_vad_trim_batch_chunked(struct mwx_vad_context* vctx,
+                                                   struct mwx_vad_params params, float chunk_s,
+                                                   const float* const* samples,
+                                                   const int* n_samples, int n_clips) {
+  if (std::isnan(chunk_s) || !(chunk_s >= 1.0f && chunk_s <= 30.0f)) {
+    MWX_LOG_ERROR("mwx_vad_trim_batch_chunked: chunk_s outside [1, 30]\n");
+    return nullptr;
+  }
+  const int64_t cap = (int64_t)((double)chunk_s * 16000.0);
+  return vad_trim_batch_any(vctx, params, cap, samples, n_samples, n_clips);
 }
 
 int mwx_vad_trimmed_n_clips(const struct mwx_vad_trimmed* t) { return t ? (int)t->clips.size() : 0; }
@@ -790,6 +863,35 @@ int64_t mwx_vad_trimmed_map_time(const struct mwx_vad_trimmed* t, int clip, int6
 }
 void mwx_vad_trimmed_free(struct mwx_vad_trimmed* t) { mwx::vad_trimmed_destroy(t); }
 
+int mwx_vad_trimmed_n_chunks(const struct mwx_vad_trimmed* t, int clip) {
+  MWX_TRIM_CLIP(t, clip, -1);
+  return (int)(t->clips[clip].chunk.size() / 2);
+}
+int mwx_vad_trimmed_chunk(const struct mwx_vad_trimmed* t, int clip, int j, int* first_segment,
+                          int* n_segments, int64_t* start, int64_t* len) {
+  MWX_TRIM_CLIP(t, clip, -1);
+  int64_t first, n, s, l;
+  if (!mwx::vad_chunk_span(t->clips[clip], j, first, n, s, l)) return -1;
+  if (first_segment) *first_segment = (int)first;
+  if (n_segments) *n_segments = (int)n;
+  if (start) *start = s;
+  if (len) *len = l;
+  return 0;
+}
+int64_t mwx_vad_trimmed_chunk_map_time(const struct mwx_vad_trimmed* t, int clip, int j,
+                                       int64_t t_cs, bool is_end) {
+  MWX_TRIM_CLIP(t, clip, t_cs);
+  return mwx::vad_chunk_map_time(t->clips[clip], j, t_cs, is_end);
+}
+
+int mwx_vad_last_chunk_kernel_ms(struct mwx_vad_context* vctx, float* chunks_ms) {
+  if (!vctx || !vctx->timed_chunks) return -1;
+  float a = 0.0f;
+  if (hipEventElapsedTime(&a, vctx->ev[6], vctx->ev[7]) != hipSuccess) return -1;
+  if (chunks_ms) *chunks_ms = a;
+  return 0;
+}
+
 int mwx_vad_last_trim_kernel_ms(struct mwx_vad_context* vctx, float* segments_ms,
                                 float* compact_ms) {
   if (!vctx || !vctx->timed_trim) return -1;
@@ -824,6 +926,37 @@ int mwx_test_vad_segments(struct mwx_vad_context* vctx, const struct mwx_vad_par
       if (c.seg.size() / 2 > (size_t)mwx_vad_n_chunks(n_samples[b])) return -5;
       std::copy(c.seg.begin(), c.seg.end(), segments + 2 * (size_t)out_offset[b]);
       std::copy(c.piece.begin(), c.piece.end(), pieces + 3 * (size_t)out_offset[b]);
+    }
+    return 0;
+  } catch (const std::exception&) {
+    return -4;
+  }
+}
+
+int mwx_test_vad_chunks(struct mwx_vad_context* vctx, const struct mwx_vad_params* params,
+                        const int64_t* caps, const float* probs, const int* probs_offset,
+                        const int* n_samples, int n_clips, int* n_chunks, int64_t* chunks,
+                        const int* out_offset) {
+  if (!vctx || n_clips <= 0 || !params || !caps || !probs || !probs_offset || !n_samples ||
+      !n_chunks || !chunks || !out_offset)
+    return -1;
+  std::vector<mwx::VadSegParams> prm((size_t)n_clips);
+  for (int b = 0; b < n_clips; ++b)
+    if (caps[b] < 1 || !mwx::vad_derive_params(params[b], prm[b])) return -2;
+  try {
+    std::vector<mwx_vad_trimmed::Clip> out;
+    const int rc = mwx::vad_segments_of_probs(vctx, prm.data(), probs, probs_offset, n_samples,
+                                              n_clips, out, caps);
+    if (rc != 0) return rc;
+    for (int b = 0; b < n_clips; ++b) {
+      const mwx_vad_trimmed::Clip& c = out[b];
+      const int64_t nc = (int64_t)c.chunk.size() / 2;
+      if (nc > mwx_vad_n_chunks(n_samples[b])) return -5;
+      n_chunks[b] = (int)nc;
+      for (int64_t j = 0; j < nc; ++j) {
+        int64_t* o = chunks + 4 * ((size_t)out_offset[b] + (size_t)j);
+        if (!mwx::vad_chunk_span(c, j, o[0], o[1], o[2], o[3])) return -5;
+      }
     }
     return 0;
   } catch (const std::exception&) {

@@ -322,6 +322,18 @@ int mwx_stt_set_audio_ctx(void* eng, int audio_ctx, int fit) {
   return static_cast<SttEngine*>(eng)->set_audio_ctx(audio_ctx, fit != 0) ? 0 : -1;
 }
 
+// Settings::vad_chunk_s / vad_chunk_batch (chunked long-form transcription,
+// DESIGN.md D10) of the requests that start after the call. chunk_s = 0 switches
+// it off. 1 = chunking now runs, 0 = set but inactive (vad_trim is not active,
+// or the library lacks the calls: the path stays vad_trim's); -1 without an
+// engine, for a chunk_s outside [1, 30] or a chunk_batch < 1 (nothing changes).
+int mwx_stt_set_vad_chunk(void* eng, float chunk_s, int chunk_batch) {
+  if (!eng) return -1;
+  SttEngine* e = static_cast<SttEngine*>(eng);
+  if (!e->set_vad_chunk(chunk_s, chunk_batch)) return -1;
+  return e->chunk_active() ? 1 : 0;
+}
+
 // 0.. = JSON length written; -1 = error; -2 = EngineBusyException;
 // < -2 = -(needed capacity). abort_after >= 0: RequestOptions::should_abort
 // answers true from its (abort_after + 1)-th call on (the service's abort

@@ -27,6 +27,10 @@
 #pragma weak mwx_vad_trimmed_n_segments
 #pragma weak mwx_vad_trimmed_free
 #pragma weak mwx_full_batch_trimmed
+// ... and the chunked calls: without them vad_chunk_s leaves the path vad_trim's
+#pragma weak mwx_vad_trim_batch_chunked
+#pragma weak mwx_vad_trimmed_n_chunks
+#pragma weak mwx_full_batch_chunked
 
 namespace mwx_host {
 
@@ -49,6 +53,16 @@ struct TrimList {
   TrimList(const TrimList&) = delete;
   TrimList& operator=(const TrimList&) = delete;
 };
+
+// mwx_full_batch_trimmed, or with chunking active (chunk_batch > 0)
+// mwx_full_batch_chunked. An object of a plain trim pass is one chunk per clip,
+// so a setting changed between the trim pass and this call is harmless.
+int full_trimmed(mwx_context* ctx, int chunk_batch, mwx_state* const* states,
+                 const mwx_full_params& p, const TrimList& objs, const int* clip_index, int n) {
+  if (chunk_batch > 0)
+    return mwx_full_batch_chunked(ctx, states, p, objs.p, clip_index, n, chunk_batch);
+  return mwx_full_batch_trimmed(ctx, states, p, objs.p, clip_index, n);
+}
 
 bool abort_trampoline(void* user_data) {
   auto* fn = static_cast<std::function<bool()>*>(user_data);
@@ -185,6 +199,13 @@ SttEngine::SttEngine(const Settings& settings) : settings_(settings) {
     trim_active_ = settings_.vad_trim && vad_ctx_ && mwx_vad_default_params &&
                    mwx_vad_trim_batch && mwx_vad_trimmed_n_segments && mwx_vad_trimmed_free &&
                    mwx_full_batch_trimmed;
+    chunk_bound_ = mwx_vad_trim_batch_chunked && mwx_vad_trimmed_n_chunks && mwx_full_batch_chunked;
+    if (settings_.vad_chunk_s != 0.0f &&
+        !set_vad_chunk(settings_.vad_chunk_s, settings_.vad_chunk_batch)) {
+      std::fprintf(stderr, "SttEngine: vad_chunk_s %g / vad_chunk_batch %d invalid, chunking off\n",
+                   settings_.vad_chunk_s, settings_.vad_chunk_batch);
+      settings_.vad_chunk_s = 0.0f;
+    }
   }
   const int pool = std::max(1, settings_.parallel_requests);
   if (settings_.max_batch > 1) {
@@ -330,8 +351,8 @@ void SttEngine::batcher_loop(std::vector<mwx_state*> states) {
       TrimList objs(batch.size());
       for (size_t b = 0; b < batch.size(); ++b) objs.p[b] = batch[b]->trimmed->t;
       const std::vector<int> first(batch.size(), 0);
-      ret = mwx_full_batch_trimmed(ctx_, states.data(), p, objs.p, first.data(),
-                                   (int)batch.size());
+      ret = full_trimmed(ctx_, chunk_batch(), states.data(), p, objs, first.data(),
+                         (int)batch.size());
     } else {
       ret = mwx_full_batch(ctx_, states.data(), p, ptrs.data(), lens.data(), (int)batch.size());
     }
@@ -528,9 +549,16 @@ std::shared_ptr<TrimmedAudio> SttEngine::trim_clips(const float* const* pcm, con
   vp.threshold = settings_.vad_threshold;
   auto out = std::make_shared<TrimmedAudio>();
   std::lock_guard<std::mutex> lock(vad_mutex_);
-  out->t = mwx_vad_trim_batch(vad_ctx_, vp, pcm, n_samples, n_clips);
+  if (chunk_active()) {
+    const float chunk_s = settings_.vad_chunk_s;
+    vp.max_speech_duration_s = std::min(vp.max_speech_duration_s, chunk_s);
+    out->t = mwx_vad_trim_batch_chunked(vad_ctx_, vp, chunk_s, pcm, n_samples, n_clips);
+  } else {
+    out->t = mwx_vad_trim_batch(vad_ctx_, vp, pcm, n_samples, n_clips);
+  }
   return out->t ? out : nullptr;
 }
+
 
 TranscriptionResult SttEngine::empty_result(size_t pcm_size) {
   TranscriptionResult r;
@@ -597,9 +625,10 @@ std::vector<TranscriptionResult> SttEngine::transcribe(const std::vector<float>&
   const mwx_full_params p = make_params(options, lang, abort_fn);
   int ret;
   if (trimmed) {
-    const mwx_vad_trimmed* obj = trimmed->t;
+    TrimList obj(1);
+    obj.p[0] = trimmed->t;
     const int first = 0;
-    ret = mwx_full_batch_trimmed(ctx_, &state, p, &obj, &first, 1);
+    ret = full_trimmed(ctx_, chunk_batch(), &state, p, obj, &first, 1);
   } else {
     ret = mwx_full_with_state(ctx_, state, p, pcm.data(), static_cast<int>(pcm_size));
   }
@@ -731,8 +760,8 @@ std::vector<std::vector<TranscriptionResult>> SttEngine::transcribe_batch(
   if (trimmed) {
     TrimList objs(run.size());
     for (size_t i = 0; i < run.size(); ++i) objs.p[i] = trimmed->t;
-    ret = mwx_full_batch_trimmed(ctx_, states.data(), p, objs.p, trim_index.data(),
-                                 static_cast<int>(run.size()));
+    ret = full_trimmed(ctx_, chunk_batch(), states.data(), p, objs, trim_index.data(),
+                       static_cast<int>(run.size()));
   } else {
     ret = mwx_full_batch(ctx_, states.data(), p, ptrs.data(), lens.data(),
                          static_cast<int>(run.size()));

@@ -99,6 +99,17 @@ struct Settings {
   // unmeasured.
   int audio_ctx = 0;
   bool audio_ctx_fit = false;
+  // Chunked long-form transcription (INTEGRATION.md "Chunked
+  // long-form transcription"), on top of vad_trim: vad_chunk_s in [1, 30] packs
+  // a clip's speech into chunks of at most that many seconds
+  // (mwx_vad_trim_batch_chunked, with max_speech_duration_s = min(its value,
+  // vad_chunk_s) so that uninterrupted speech is still cut) and decodes them
+  // side by side, at most vad_chunk_batch per engine run
+  // (mwx_full_batch_chunked). 0 = off. Active only with vad_trim active and a
+  // library that has the calls; otherwise the path is vad_trim's. Streaming
+  // sessions do not chunk.
+  float vad_chunk_s = 0.0f;
+  int vad_chunk_batch = 32;
 };
 
 // Reads the DTW settings from the environment, as the service reads its other
@@ -218,6 +229,19 @@ class SttEngine {
     return true;
   }
 
+  // Settings::vad_chunk_s / vad_chunk_batch of the requests that start after
+  // the call (as set_audio_ctx: set it before serving). chunk_s = 0 switches
+  // chunking off; false, and nothing changed, for a chunk_s outside [1, 30]
+  // or a batch < 1. Whether chunking then runs: chunk_active().
+  bool set_vad_chunk(float chunk_s, int chunk_batch) {
+    if (chunk_s != chunk_s || chunk_batch < 1) return false;
+    if (chunk_s != 0.0f && !(chunk_s >= 1.0f && chunk_s <= 30.0f)) return false;
+    settings_.vad_chunk_s = chunk_s;
+    settings_.vad_chunk_batch = chunk_batch;
+    return true;
+  }
+  bool chunk_active() const { return trim_active_ && chunk_bound_ && settings_.vad_chunk_s > 0.0f; }
+
   struct PerformanceMetrics {
     double queue_time_ms;
     double processing_time_ms;
@@ -296,6 +320,10 @@ class SttEngine {
   std::shared_ptr<TrimmedAudio> trim_clips(const float* const* pcm, const int* n_samples,
                                               int n_clips);
   bool trim_active_ = false;  // vad_trim, a VAD context and a library that has the calls
+  bool chunk_bound_ = false;  // the library has the chunked calls
+  // the chunk batch of the engine call over trimmed audio: > 0 with chunking
+  // active (mwx_full_batch_chunked), 0 for mwx_full_batch_trimmed
+  int chunk_batch() const { return chunk_active() ? settings_.vad_chunk_batch : 0; }
 
   // the one result of a clip the VAD gate holds back (src/stt_engine.cpp:172-183)
   static TranscriptionResult empty_result(size_t pcm_size);

@@ -380,6 +380,23 @@ def lib() -> C.CDLL:
                                         i64p, i64p, ip]
     L.mwx_test_vad_trimmed_pcm.restype = C.c_int64
     L.mwx_test_vad_trimmed_pcm.argtypes = [P, C.c_int, fpp, C.c_int64]
+    L.mwx_vad_trim_batch_chunked.restype = P
+    L.mwx_vad_trim_batch_chunked.argtypes = [P, VadParams, C.c_float, C.POINTER(C.c_void_p), ip,
+                                             C.c_int]
+    L.mwx_vad_trimmed_n_chunks.restype = C.c_int
+    L.mwx_vad_trimmed_n_chunks.argtypes = [P, C.c_int]
+    L.mwx_vad_trimmed_chunk.restype = C.c_int
+    L.mwx_vad_trimmed_chunk.argtypes = [P, C.c_int, C.c_int, ip, ip, i64p, i64p]
+    L.mwx_vad_trimmed_chunk_map_time.restype = C.c_int64
+    L.mwx_vad_trimmed_chunk_map_time.argtypes = [P, C.c_int, C.c_int, C.c_int64, C.c_bool]
+    L.mwx_vad_last_chunk_kernel_ms.restype = C.c_int
+    L.mwx_vad_last_chunk_kernel_ms.argtypes = [P, fpp]
+    L.mwx_full_batch_chunked.restype = C.c_int
+    L.mwx_full_batch_chunked.argtypes = [P, C.POINTER(P), FullParams, C.POINTER(P), ip, C.c_int,
+                                         C.c_int]
+    L.mwx_test_vad_chunks.restype = C.c_int
+    L.mwx_test_vad_chunks.argtypes = [P, C.POINTER(VadParams), i64p, fpp, ip, ip, C.c_int, ip,
+                                      i64p, ip]
     _lib = L
     return L
 
@@ -622,6 +639,16 @@ class Context:
         objs = (C.c_void_p * n)(*[t.t for t in trimmed])
         idx = (C.c_int * n)(*clip_index)
         return lib().mwx_full_batch_trimmed(self.ctx, states, params, objs, idx, n)
+
+    def full_batch_chunked(self, trimmed: Sequence["VadTrimmed"], clip_index: Sequence[int],
+                           params: FullParams, max_batch: int = 32, state0: int = 0) -> int:
+        """mwx_full_batch_chunked: as full_batch_trimmed, every chunk of every
+        entry decoded as a batch entry of its own, at most max_batch per run."""
+        n = len(trimmed)
+        states = (C.c_void_p * n)(*[self.state(state0 + i) for i in range(n)])
+        objs = (C.c_void_p * n)(*[t.t for t in trimmed])
+        idx = (C.c_int * n)(*clip_index)
+        return lib().mwx_full_batch_chunked(self.ctx, states, params, objs, idx, n, max_batch)
 
     def segments(self, state_index: int = 0) -> List[Segment]:
         L = lib()
@@ -1379,16 +1406,53 @@ class VadContext:
         return self._segments(lib().mwx_vad_segments_from_samples(
             self.vctx, params or vad_params(), addr, n))
 
-    def trim_batch(self, pcms, params: Optional[VadParams] = None) -> "VadTrimmed":
-        """mwx_vad_trim_batch: VAD, segments and compaction of every clip."""
+    def trim_batch(self, pcms, params: Optional[VadParams] = None,
+                   chunk_s: Optional[float] = None) -> "VadTrimmed":
+        """mwx_vad_trim_batch: VAD, segments and compaction of every clip. With
+        chunk_s, mwx_vad_trim_batch_chunked: plus the chunk plan."""
         clips = [self._clip(p) for p in pcms]
         n = len(clips)
         ptrs = (C.c_void_p * max(n, 1))(*[c[1] for c in clips])
         lens = (C.c_int * max(n, 1))(*[c[2] for c in clips])
-        t = lib().mwx_vad_trim_batch(self.vctx, params or vad_params(), ptrs, lens, n)
+        if chunk_s is None:
+            t = lib().mwx_vad_trim_batch(self.vctx, params or vad_params(), ptrs, lens, n)
+        else:
+            t = lib().mwx_vad_trim_batch_chunked(self.vctx, params or vad_params(), chunk_s, ptrs,
+                                                 lens, n)
         if not t:
             raise RuntimeError("mwx_vad_trim_batch failed")
         return VadTrimmed(t)
+
+    def last_chunk_kernel_ms(self) -> float:
+        """vad_chunks_kernel's device milliseconds in the last chunked trim_batch."""
+        a = C.c_float()
+        if lib().mwx_vad_last_chunk_kernel_ms(self.vctx, C.byref(a)) != 0:
+            raise RuntimeError("mwx_vad_last_chunk_kernel_ms: no timed call")
+        return a.value
+
+    def test_chunks(self, probs: Sequence[np.ndarray], n_samples: Sequence[int],
+                    params: Sequence[VadParams], caps: Sequence[int]):
+        """mwx_test_vad_chunks: vad_segments_kernel, then vad_chunks_kernel over
+        given probabilities, clip b with cap caps[b] in samples. Per clip:
+        [(first piece, n pieces, start, len), ...]."""
+        n = len(probs)
+        arrs = [np.ascontiguousarray(p, np.float32) for p in probs]
+        offs = np.concatenate([[0], np.cumsum([len(a) for a in arrs])]).astype(np.int32)
+        flat = np.concatenate(arrs + [np.zeros(1, np.float32)])
+        ns = np.ascontiguousarray(n_samples, np.int32)
+        cp = np.ascontiguousarray(caps, np.int64)
+        prm = (VadParams * n)(*params)
+        nch = np.zeros(n, np.int32)
+        out = np.zeros(4 * max(1, int(offs[-1])), np.int64)
+        ip, i64p = C.POINTER(C.c_int), C.POINTER(C.c_int64)
+        rc = lib().mwx_test_vad_chunks(self.vctx, prm, cp.ctypes.data_as(i64p), fptr(flat),
+                                       offs.ctypes.data_as(ip), ns.ctypes.data_as(ip), n,
+                                       nch.ctypes.data_as(ip), out.ctypes.data_as(i64p),
+                                       offs.ctypes.data_as(ip))
+        if rc != 0:
+            raise RuntimeError(f"mwx_test_vad_chunks failed ({rc})")
+        return [[tuple(int(v) for v in out[4 * (int(offs[b]) + j):4 * (int(offs[b]) + j) + 4])
+                 for j in range(int(nch[b]))] for b in range(n)]
 
     def last_trim_kernel_ms(self):
         """(segments, compaction) device milliseconds of the last trim_batch."""
@@ -1475,6 +1539,22 @@ class VadTrimmed:
 
     def map_time(self, clip: int, t_cs: int, is_end: bool) -> int:
         return lib().mwx_vad_trimmed_map_time(self.t, clip, t_cs, is_end)
+
+    def chunks(self, clip: int) -> List[tuple]:
+        """[(first segment, n segments, start, len), ...]: the clip's chunk plan,
+        start and len in samples of the compacted clip."""
+        L = lib()
+        out = []
+        for j in range(L.mwx_vad_trimmed_n_chunks(self.t, clip)):
+            f, n, a, b = C.c_int(), C.c_int(), C.c_int64(), C.c_int64()
+            if L.mwx_vad_trimmed_chunk(self.t, clip, j, C.byref(f), C.byref(n), C.byref(a),
+                                       C.byref(b)) != 0:
+                raise RuntimeError("mwx_vad_trimmed_chunk failed")
+            out.append((f.value, n.value, a.value, b.value))
+        return out
+
+    def chunk_map_time(self, clip: int, j: int, t_cs: int, is_end: bool) -> int:
+        return lib().mwx_vad_trimmed_chunk_map_time(self.t, clip, j, t_cs, is_end)
 
     def pcm(self, clip: int) -> np.ndarray:
         """mwx_test_vad_trimmed_pcm: the compacted clip, copied to the host."""
