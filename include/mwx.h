@@ -642,6 +642,62 @@ int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* sta
                            const struct mwx_vad_trimmed* const* trimmed, const int* clip_index,
                            int n_clips, int max_batch);
 
+/* --- streaming VAD ---------------------------------------------------------------
+ * A stream is fed a piece of 16 kHz audio at a time and carries the network's
+ * recurrent state, the samples that do not fill a 512-sample chunk yet and the
+ * segment scan across the calls (csrc/k_vad.hip,
+ * vad_stream_stage_kernel / vad_lstm_stream_kernel / vad_stream_scan_kernel).
+ * Two invariants:
+ *   1. After any sequence of feeds, mwx_vad_stream_probs holds the bits that
+ *      mwx_vad_detect_speech returns for everything fed since the last reset,
+ *      the last chunk included when it is partial: that one is computed
+ *      zero-padded as a provisional step whose state is not kept, replaced when
+ *      the chunk completes, and not seen by the scan.
+ *   2. The raw segments closed so far, followed by mwx_vad_stream_finish, are
+ *      the segments of rule D7 over those probabilities before its padding
+ *      pass; padded as D7 pads they are mwx_vad_segments_from_samples of the
+ *      whole audio. The stream does not pad: padding looks ahead.
+ * A stream belongs to its context and shares the context's rule of one call at
+ * a time (init, free, reset and feed count as calls). Free the streams before
+ * the context; a stream that outlives it accepts only mwx_vad_stream_free. */
+struct mwx_vad_stream;
+/* NULL (logged) on the parameter errors mwx_vad_segments_from_probs refuses, or
+ * a device error. */
+struct mwx_vad_stream* mwx_vad_stream_init(struct mwx_vad_context* vctx,
+                                           struct mwx_vad_params params);
+void mwx_vad_stream_free(struct mwx_vad_stream* s);
+/* As new: h = c = 0, position 0, no tail, scan cleared, no probabilities or
+ * segments. 0, or < 0 without a stream or a context. */
+int mwx_vad_stream_reset(struct mwx_vad_stream* s);
+/* Appends n_samples[i] samples (host or device memory; 0 allowed; at most
+ * 480000 per stream per call) to streams[i], all streams in one pass of the
+ * kernels and one copy back. A stream may appear once per call. The result of
+ * a stream does not depend on which others share the call. 0, or < 0 on bad
+ * arguments, a finished stream or a stream of another context (no stream of
+ * the call has changed) or a device error (reset the streams of the call). */
+int mwx_vad_stream_feed_batch(struct mwx_vad_context* vctx, struct mwx_vad_stream* const* streams,
+                              const float* const* samples, const int* n_samples, int n_streams);
+/* Applies rule D7's tail rule with N = the samples fed: speech still open
+ * closes at N if it is long enough. Afterwards only reset and free. */
+int mwx_vad_stream_finish(struct mwx_vad_stream* s);
+int64_t mwx_vad_stream_n_samples(const struct mwx_vad_stream* s);
+int mwx_vad_stream_n_probs(const struct mwx_vad_stream* s); /* mwx_vad_n_chunks(n_samples) */
+/* All probabilities since reset; valid until the stream's next call. */
+const float* mwx_vad_stream_probs(const struct mwx_vad_stream* s);
+float mwx_vad_stream_max_prob(const struct mwx_vad_stream* s); /* over those; 0 when none */
+int mwx_vad_stream_n_segments(const struct mwx_vad_stream* s); /* raw segments closed since reset */
+/* Raw (unpadded) segment i in samples since reset. closed_at = 512 * (index of
+ * the chunk whose step closed it + 1), or n_samples for the one
+ * mwx_vad_stream_finish closes. 0, or < 0 out of range. Outputs are nullable. */
+int mwx_vad_stream_segment(const struct mwx_vad_stream* s, int i, int64_t* s0, int64_t* s1,
+                           int64_t* closed_at);
+bool mwx_vad_stream_in_speech(const struct mwx_vad_stream* s); /* the scan's `triggered` */
+/* Device time of the last mwx_vad_stream_feed_batch in milliseconds: staging,
+ * front end, recurrence + head (the scan kernel behind them is not timed). 0 on
+ * success, -1 if the last call was none or launched nothing. */
+int mwx_vad_stream_last_kernel_ms(struct mwx_vad_context* vctx, float* stage_ms,
+                                  float* frontend_ms, float* lstm_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -371,6 +371,18 @@ int mwx_test_vad_chunks(struct mwx_vad_context* vctx, const struct mwx_vad_param
                         const int* n_samples, int n_clips, int* n_chunks, int64_t* chunks,
                         const int* out_offset);
 
+/* vad_stream_scan_kernel (the online scan of a stream) on
+ * caller-supplied probabilities that bypass the net: a stream of `vctx` with
+ * `params` receives the n_probs probabilities as whole chunks in n_splits
+ * calls of splits[k] >= 0 chunks each (their sum = n_probs). Out: *n_events and
+ * the events as (start, end, closed_at) triples (room for n_probs of them),
+ * and state[6] = the scan's registers after the last call (trig, start,
+ * temp_end, prev_end, next_start, chunk count). The tail rule is not applied.
+ * Returns 0 or < 0. */
+int mwx_test_vad_stream_scan(struct mwx_vad_context* vctx, const struct mwx_vad_params* params,
+                             const float* probs, int n_probs, const int* splits, int n_splits,
+                             int* n_events, int64_t* events, int64_t* state);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,11 @@
 // the probabilities, padding, the piece layout of the compacted clip) and
 // vad_compact_kernel (gathers the pieces of every clip into one dense buffer).
 //
+// Three serve streams that are fed a piece at a time:
+// vad_stream_stage_kernel, vad_lstm_stream_kernel (the same step with h and c
+// carried in the stream's slot) and vad_stream_scan_kernel (the segment rule's
+// scan, one chunk per step, with its registers carried too).
+//
 // All arithmetic is f32. Every output is one fixed chain of fmaf over its
 // inputs in index order, so a chunk's result does not depend on its slot in a
 // tile or on which other clips are in the launch: a batch gives the bits of
@@ -193,10 +198,42 @@ __global__ __launch_bounds__(VAD_FE_THREADS) void vad_frontend_kernel(
   }
 }
 
-// One workgroup per clip. Step: every thread adds its W_hh row . h to its
-// pre-activation and posts the gate in LDS; after the barrier threads 0..127
-// (waves 0, 1) update c and h for their unit, publish h and reduce
-// w_f . relu(h); after the second barrier thread 0 writes the probability.
+// One step of the recurrence, shared by vad_lstm_kernel and
+// vad_lstm_stream_kernel: every thread adds its W_hh row . h to its
+// pre-activation `cur` and posts the gate in LDS; after the barrier threads
+// 0..127 (waves 0, 1) update c and h for their unit, publish h and reduce
+// w_f . relu(h) into sp; the second barrier ends the step. The probability is
+// sigmoid((sp[0] + sp[1]) + b_f).
+__device__ __forceinline__ void vad_lstm_step(const float (&w)[VAD_HID], float cur, float wf, int j,
+                                              float& c, float& h, float* sh, float* sg,
+                                              float* sp) {
+  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+#pragma unroll
+  for (int q = 0; q < VAD_HID / 4; ++q) {
+    const float4 hv = *reinterpret_cast<const float4*>(&sh[4 * q]);
+    a0 = fmaf(w[4 * q + 0], hv.x, a0);
+    a1 = fmaf(w[4 * q + 1], hv.y, a1);
+    a2 = fmaf(w[4 * q + 2], hv.z, a2);
+    a3 = fmaf(w[4 * q + 3], hv.w, a3);
+  }
+  sg[j] = cur + ((a0 + a1) + (a2 + a3));
+  __syncthreads();  // gates posted; every read of h for this step is done
+  if (j < VAD_HID) {
+    const float gi = sigmoidf_acc(sg[j]);
+    const float gf = sigmoidf_acc(sg[VAD_HID + j]);
+    const float gg = tanhf(sg[2 * VAD_HID + j]);
+    const float go = sigmoidf_acc(sg[3 * VAD_HID + j]);
+    c = gf * c + gi * gg;
+    h = go * tanhf(c);
+    sh[j] = h;
+    const float part = wave_sum(wf * fmaxf(h, 0.0f));
+    if ((j & 63) == 0) sp[j >> 6] = part;
+  }
+  __syncthreads();  // h and the head's two partial sums posted
+}
+
+// One workgroup per clip: 512 threads, thread j keeps row j of W_hh in
+// registers for the whole clip; thread 0 writes each step's probability.
 __global__ __launch_bounds__(VAD_GATES) void vad_lstm_kernel(
     const float* __restrict__ whh_t, const float* __restrict__ w_f, float b_f,
     const float* __restrict__ pre, const int* __restrict__ chunk_off, int n_clips,
@@ -214,7 +251,7 @@ __global__ __launch_bounds__(VAD_GATES) void vad_lstm_kernel(
 #pragma unroll
   for (int k = 0; k < VAD_HID; ++k) w[k] = whh_t[k * VAD_GATES + j];
   const float wf = j < VAD_HID ? w_f[j] : 0.0f;
-  float c = 0.0f;
+  float c = 0.0f, h = 0.0f;
   if (j < VAD_HID) sh[j] = 0.0f;
   __syncthreads();
   const float* __restrict__ pj = pre + (size_t)off * VAD_GATES + j;
@@ -222,30 +259,205 @@ __global__ __launch_bounds__(VAD_GATES) void vad_lstm_kernel(
   for (int s = 0; s < nch; ++s) {
     const float cur = nxt;
     if (s + 1 < nch) nxt = pj[(size_t)(s + 1) * VAD_GATES];
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-#pragma unroll
-    for (int q = 0; q < VAD_HID / 4; ++q) {
-      const float4 hv = *reinterpret_cast<const float4*>(&sh[4 * q]);
-      a0 = fmaf(w[4 * q + 0], hv.x, a0);
-      a1 = fmaf(w[4 * q + 1], hv.y, a1);
-      a2 = fmaf(w[4 * q + 2], hv.z, a2);
-      a3 = fmaf(w[4 * q + 3], hv.w, a3);
-    }
-    sg[j] = cur + ((a0 + a1) + (a2 + a3));
-    __syncthreads();  // gates posted; every read of h for this step is done
-    if (j < VAD_HID) {
-      const float gi = sigmoidf_acc(sg[j]);
-      const float gf = sigmoidf_acc(sg[VAD_HID + j]);
-      const float gg = tanhf(sg[2 * VAD_HID + j]);
-      const float go = sigmoidf_acc(sg[3 * VAD_HID + j]);
-      c = gf * c + gi * gg;
-      const float h = go * tanhf(c);
-      sh[j] = h;
-      const float part = wave_sum(wf * fmaxf(h, 0.0f));
-      if ((j & 63) == 0) sp[j >> 6] = part;
-    }
-    __syncthreads();  // h and the head's two partial sums posted
+    vad_lstm_step(w, cur, wf, j, c, h, sh, sg, sp);
     if (j == 0) probs[(size_t)off + s] = sigmoidf_acc((sp[0] + sp[1]) + b_f);
+  }
+}
+
+// ---- streaming ------------------------------------------------------------------
+// A stream is fed a piece at a time and keeps what crosses a chunk boundary in
+// its VadStreamSlot: h and c of the recurrence, the samples that do not fill a
+// chunk yet, the chunk count and the registers of the segment scan. One call
+// (VadStreamFeed per stream) runs three kernels of this section around the
+// unchanged vad_frontend_kernel.
+
+// Lays [tail | new samples] of every stream out as whole 512-sample chunks in
+// `stage` (stream b's at stage + 512 chunk_off[b]); a remainder makes one more,
+// provisional chunk that is zero-filled past the last sample. The samples of
+// the remainder become the new tail, written to the other of the slot's two
+// tail buffers: other workgroups of this launch still read the old one.
+// grid.x = n_streams * tiles, tiles = ceil(512 max_chunks / VAD_ST_TILE).
+constexpr int VAD_ST_THREADS = 256;
+constexpr int VAD_ST_TILE = 2048;
+
+__global__ __launch_bounds__(VAD_ST_THREADS) void vad_stream_stage_kernel(
+    const VadStreamFeed* __restrict__ feeds, const int* __restrict__ chunk_off, int n_streams,
+    int tiles, float* __restrict__ stage) {
+  const int b = blockIdx.x / tiles;
+  if (b >= n_streams) return;
+  const int off = chunk_off[b];
+  const int len = (chunk_off[b + 1] - off) * VAD_CHUNK;  // staged samples, zeros included
+  const int x0 = (blockIdx.x % tiles) * VAD_ST_TILE;
+  if (x0 >= len) return;
+  const VadStreamFeed F = feeds[b];
+  const int total = F.tail_n + F.n_new;
+  const int keep0 = F.n_full * VAD_CHUNK;  // first sample of the new tail
+  const float* __restrict__ old_tail = F.slot->tail[F.par];
+  float* __restrict__ new_tail = F.slot->tail[F.par ^ 1];
+  const float* __restrict__ src = F.src;
+  float* __restrict__ out = stage + (size_t)off * VAD_CHUNK;
+  const int x1 = min(len, x0 + VAD_ST_TILE);
+  for (int p = x0 + (int)threadIdx.x; p < x1; p += VAD_ST_THREADS) {
+    float v = 0.0f;
+    if (p < F.tail_n)
+      v = old_tail[p];
+    else if (p < total)
+      v = src[p - F.tail_n];
+    out[p] = v;
+    if (p >= keep0 && p < total) new_tail[p - keep0] = v;
+  }
+}
+
+// vad_lstm_kernel's step over the staged chunks of every stream, one workgroup
+// per stream: h and c come from the slot (zeros for a stream that has no
+// committed chunk yet) and go back to it after the last whole chunk; the step
+// of a provisional chunk runs from there and leaves only its probability.
+__global__ __launch_bounds__(VAD_GATES) void vad_lstm_stream_kernel(
+    const float* __restrict__ whh_t, const float* __restrict__ w_f, float b_f,
+    const float* __restrict__ pre, const VadStreamFeed* __restrict__ feeds,
+    const int* __restrict__ chunk_off, int n_streams, float* __restrict__ probs) {
+  __shared__ __attribute__((aligned(16))) float sh[VAD_HID];
+  __shared__ float sg[VAD_GATES];
+  __shared__ float sp[2];
+  const int b = blockIdx.x;
+  if (b >= n_streams) return;
+  const int off = chunk_off[b];
+  const int nch = chunk_off[b + 1] - off;
+  if (nch <= 0) return;
+  VadStreamSlot* __restrict__ slot = feeds[b].slot;
+  const bool fresh = feeds[b].fresh != 0;
+  const int n_full = feeds[b].n_full;
+  const int j = threadIdx.x;
+  float w[VAD_HID];
+#pragma unroll
+  for (int k = 0; k < VAD_HID; ++k) w[k] = whh_t[k * VAD_GATES + j];
+  const float wf = j < VAD_HID ? w_f[j] : 0.0f;
+  float c = 0.0f, h = 0.0f;
+  if (j < VAD_HID) {
+    sh[j] = fresh ? 0.0f : slot->h[j];
+    c = fresh ? 0.0f : slot->c[j];
+  }
+  __syncthreads();
+  const float* __restrict__ pj = pre + (size_t)off * VAD_GATES + j;
+  float nxt = pj[0];
+  for (int s = 0; s < nch; ++s) {
+    const float cur = nxt;
+    if (s + 1 < nch) nxt = pj[(size_t)(s + 1) * VAD_GATES];
+    vad_lstm_step(w, cur, wf, j, c, h, sh, sg, sp);
+    if (j == 0) probs[(size_t)off + s] = sigmoidf_acc((sp[0] + sp[1]) + b_f);
+    if (s == n_full - 1 && j < VAD_HID) {
+      slot->h[j] = h;
+      slot->c[j] = c;
+    }
+  }
+}
+
+// The loop body of vad_segments_kernel's scan (rule D7), one chunk per step,
+// over the whole chunks a call added, with the scan's registers kept in the
+// slot between calls: one wave per stream, masks and walk as in that kernel.
+// A segment the scan closes is appended raw (no padding: that looks ahead) as
+// (start, end, closed_at), closed_at = the end of the chunk whose step closed
+// it; a step closes at most one. Lane 0 stores. out: per stream a header of
+// VAD_STREAM_HDR int64 (event count, trig, start, temp_end, prev_end,
+// next_start, chunk count), then stream b's events at
+// out + VAD_STREAM_HDR n_streams + 3 chunk_off[b].
+__global__ __launch_bounds__(64) void vad_stream_scan_kernel(
+    const float* __restrict__ probs, const VadStreamFeed* __restrict__ feeds,
+    const int* __restrict__ chunk_off, int n_streams, long long* __restrict__ out) {
+  const int b = blockIdx.x;
+  if (b >= n_streams) return;
+  const int lane = threadIdx.x;
+  const int off = chunk_off[b];
+  const VadStreamFeed F = feeds[b];
+  const int nch = min(F.n_full, chunk_off[b + 1] - off);  // the provisional chunk is not scanned
+  const VadSegParams P = F.prm;
+  VadStreamSlot* __restrict__ slot = F.slot;
+  long long* __restrict__ hdr = out + (size_t)VAD_STREAM_HDR * b;
+  long long* __restrict__ ev = out + (size_t)VAD_STREAM_HDR * n_streams + 3 * (size_t)off;
+
+  bool trig = false;
+  long long start = 0, temp_end = 0, prev_end = 0, next_start = 0, chunk0 = 0;
+  if (!F.fresh) {
+    trig = slot->trig != 0;
+    start = slot->start;
+    temp_end = slot->temp_end;
+    prev_end = slot->prev_end;
+    next_start = slot->next_start;
+    chunk0 = slot->n_chunks;
+  }
+  int m = 0;
+  long long closed_at = 0;
+  auto emit = [&](long long s, long long e) {
+    if (lane == 0 && m < nch) {
+      ev[3 * m] = s;
+      ev[3 * m + 1] = e;
+      ev[3 * m + 2] = closed_at;
+    }
+    ++m;
+  };
+  const float* __restrict__ p = probs + off;
+  float nxt = lane < nch ? p[lane] : 0.0f;
+  for (int base = 0; base < nch; base += 64) {
+    const float v = nxt;
+    const bool valid = base + lane < nch;
+    if (base + 64 + lane < nch) nxt = p[base + 64 + lane];
+    const unsigned long long ms = __ballot(valid && v >= P.thr);
+    const unsigned long long ml = __ballot(valid && v < P.neg);
+    const int cnt = min(64, nch - base);
+    for (int j = 0; j < cnt; ++j) {
+      const bool sp = (ms >> j) & 1, sl = (ml >> j) & 1;
+      const long long cur = (long long)VAD_CHUNK * (chunk0 + base + j);
+      closed_at = cur + VAD_CHUNK;
+      if (sp && temp_end != 0) {
+        temp_end = 0;
+        if (next_start < prev_end) next_start = cur;
+      }
+      if (sp && !trig) {
+        trig = true;
+        start = cur;
+        continue;
+      }
+      if (trig && cur - start > P.max_speech) {
+        if (prev_end > 0) {
+          emit(start, prev_end);
+          if (next_start < prev_end)
+            trig = false;
+          else
+            start = next_start;
+          prev_end = next_start = temp_end = 0;
+        } else {
+          emit(start, cur);
+          prev_end = next_start = temp_end = 0;
+          trig = false;
+          continue;
+        }
+      }
+      if (sl && trig) {
+        if (temp_end == 0) temp_end = cur;
+        if (cur - temp_end > VAD_SIL_AT_MAX) prev_end = temp_end;
+        if (cur - temp_end < P.min_sil) continue;
+        if (temp_end - start > P.min_speech) emit(start, temp_end);
+        prev_end = next_start = temp_end = 0;
+        trig = false;
+      }
+    }
+  }
+  if (lane == 0) {
+    const long long n_chunks = chunk0 + nch;
+    slot->trig = trig ? 1 : 0;
+    slot->start = start;
+    slot->temp_end = temp_end;
+    slot->prev_end = prev_end;
+    slot->next_start = next_start;
+    slot->n_chunks = n_chunks;
+    hdr[0] = min(m, nch);
+    hdr[1] = trig ? 1 : 0;
+    hdr[2] = start;
+    hdr[3] = temp_end;
+    hdr[4] = prev_end;
+    hdr[5] = next_start;
+    hdr[6] = n_chunks;
+    hdr[7] = 0;
   }
 }
 
@@ -478,6 +690,27 @@ void vad_lstm_launch(const VadWeights& w, const float* pre, const int* chunk_off
   if (n_clips <= 0) return;
   vad_lstm_kernel<<<n_clips, VAD_GATES, 0, st>>>(w.whh_t, w.w_f, w.b_f, pre, chunk_off, n_clips,
                                                  probs);
+}
+
+void vad_stream_stage_launch(const VadStreamFeed* feeds, const int* chunk_off, int n_streams,
+                             int max_chunks, float* stage, hipStream_t st) {
+  if (n_streams <= 0 || max_chunks <= 0) return;
+  const long tiles = ((long)max_chunks * VAD_CHUNK + VAD_ST_TILE - 1) / VAD_ST_TILE;
+  vad_stream_stage_kernel<<<(unsigned)(tiles * n_streams), VAD_ST_THREADS, 0, st>>>(
+      feeds, chunk_off, n_streams, (int)tiles, stage);
+}
+
+void vad_lstm_stream_launch(const VadWeights& w, const float* pre, const VadStreamFeed* feeds,
+                            const int* chunk_off, int n_streams, float* probs, hipStream_t st) {
+  if (n_streams <= 0) return;
+  vad_lstm_stream_kernel<<<n_streams, VAD_GATES, 0, st>>>(w.whh_t, w.w_f, w.b_f, pre, feeds,
+                                                          chunk_off, n_streams, probs);
+}
+
+void vad_stream_scan_launch(const float* probs, const VadStreamFeed* feeds, const int* chunk_off,
+                            int n_streams, long long* out, hipStream_t st) {
+  if (n_streams <= 0) return;
+  vad_stream_scan_kernel<<<n_streams, 64, 0, st>>>(probs, feeds, chunk_off, n_streams, out);
 }
 
 void vad_segments_launch(const float* probs, const int* n_samples, const int* chunk_off,

@@ -572,4 +572,43 @@ void vad_compact_launch(const float* const* pcm, const int* n_samples, const int
                         int n_clips, const long long* tables, const long long* out_off,
                         long long max_len, float* out, hipStream_t st);
 
+// Streaming VAD (k_vad.hip). What a stream keeps on the device
+// between two calls:
+struct VadStreamSlot {
+  float h[VAD_HID], c[VAD_HID];  // the recurrence after the last whole chunk
+  float tail[2][VAD_CHUNK];      // the samples that do not fill a chunk yet; a call
+                                 // reads buffer `par` and writes the other
+  long long n_chunks;            // whole chunks since reset
+  long long start, temp_end, prev_end, next_start;  // the scan's registers (rule D7)
+  int trig, pad_;
+};
+// One stream's part of one call. The host mirrors tail_n and the chunk count,
+// so the split into whole chunks is made there.
+struct VadStreamFeed {
+  VadStreamSlot* slot;
+  const float* src;  // n_new new samples (device memory)
+  int n_new, tail_n; // tail_n < 512 samples wait in slot->tail[par]
+  int par;
+  int fresh;         // no whole chunk since reset: h = c = 0, scan registers 0
+  int n_full;        // whole chunks of [tail | new]: committed by this call
+  int rem;           // (tail_n + n_new) % 512: > 0 adds one provisional chunk
+  VadSegParams prm;
+};
+constexpr int VAD_STREAM_HDR = 8;  // int64 words per stream before the events
+// chunk_off: n_streams + 1 prefix sums of the staged chunks (n_full + (rem > 0)).
+// stage receives stream b's chunks at stage + 512 chunk_off[b], ready for
+// vad_frontend_launch as a clip of tail_n + n_new samples.
+void vad_stream_stage_launch(const VadStreamFeed* feeds, const int* chunk_off, int n_streams,
+                             int max_chunks, float* stage, hipStream_t st);
+// vad_lstm_launch with h and c carried in the slots; the provisional chunk's
+// step is not committed.
+void vad_lstm_stream_launch(const VadWeights& w, const float* pre, const VadStreamFeed* feeds,
+                            const int* chunk_off, int n_streams, float* probs, hipStream_t st);
+// The scan of rule D7 over each stream's n_full new probabilities. out: int64
+// [VAD_STREAM_HDR n_streams + 3 total chunks]: per stream (events, trig, start,
+// temp_end, prev_end, next_start, chunk count, 0), then stream b's events
+// (start, end, closed_at) from word VAD_STREAM_HDR n_streams + 3 chunk_off[b].
+void vad_stream_scan_launch(const float* probs, const VadStreamFeed* feeds, const int* chunk_off,
+                            int n_streams, long long* out, hipStream_t st);
+
 }  // namespace mwx

@@ -1,7 +1,8 @@
 // Voice-activity detection: the model file (reader and seeded writer), the
 // VAD context and the mwx_vad_* entry points of include/mwx.h, speech segments
 // and silence trimming (mwx_vad_segments_*, mwx_vad_trim_batch) and the chunk
-// plan of a long clip (mwx_vad_trim_batch_chunked) included. The
+// plan of a long clip (mwx_vad_trim_batch_chunked) included, and
+// the streams that are fed a piece at a time (mwx_vad_stream_*, D11). The
 // kernels are in k_vad.hip; the network, the file layout and the segment rule
 // are written down in INTEGRATION.md ("VAD model", "VAD speech segments").
 #include <hip/hip_runtime.h>
@@ -248,14 +249,39 @@ struct mwx_vad_context {
   int device = 0;
   hipStream_t stream = nullptr;
   // front end | recurrence | segments, around the compaction, around the chunk plan
-  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool timed = false, timed_trim = false, timed_chunks = false;
+  // ... and [8..11] around the three network kernels of a stream call
+  hipEvent_t ev[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool timed = false, timed_trim = false, timed_chunks = false, timed_stream = false;
   float* d_weights = nullptr;
   mwx::VadWeights w{};
   mwx::VBuf d_pcm, d_pre, d_probs, d_meta, d_tab, d_ooff, d_ctab, d_caps;
   mwx::PinBuf h_meta, h_probs, h_tab, h_ooff, h_ctab, h_caps;
   std::vector<float> probs;  // mwx_vad_probs
   int probs_n_samples = 0;   // the clip length they belong to
+  // streams: the slot table grows a block at a time, so a
+  // stream's slot never moves; a freed slot is handed out again
+  std::vector<mwx::VadStreamSlot*> slot_blocks;
+  std::vector<mwx::VadStreamSlot*> free_slots;
+  std::vector<mwx_vad_stream*> streams;  // live ones: orphaned when the context goes first
+  mwx::VBuf d_stage, d_sout;
+  mwx::PinBuf h_sout;
+};
+
+struct mwx_vad_stream {
+  mwx_vad_context* ctx = nullptr;  // null once its context is freed
+  mwx::VadStreamSlot* slot = nullptr;
+  mwx::VadSegParams prm{};
+  // host mirror of the slot: what splits a feed into chunks, and the scan's
+  // registers as of the last call (mwx_vad_stream_finish needs trig and start)
+  int64_t n_samples = 0, n_chunks = 0;
+  int tail_n = 0, par = 0;
+  bool finished = false, provisional = false;
+  bool trig = false;
+  int64_t start = 0, temp_end = 0, prev_end = 0, next_start = 0;
+  std::vector<float> probs;  // all since reset; the last one provisional when `provisional`
+  float max_whole = 0.0f;    // over the whole chunks' probabilities
+  std::vector<int64_t> seg;  // raw segments closed since reset: (s0, s1, closed_at)
 };
 
 namespace mwx {
@@ -279,9 +305,14 @@ void vad_destroy(mwx_vad_context* v) {
   v->h_probs.release();
   v->h_tab.release();
   v->h_ooff.release();
+  v->d_stage.release();
+  v->d_sout.release();
+  v->h_sout.release();
+  for (mwx_vad_stream* s : v->streams) s->ctx = nullptr;
   {
     std::lock_guard<std::recursive_mutex> lock(capture_mutex());
     if (v->d_weights) (void)hipFree(v->d_weights);
+    for (VadStreamSlot* b : v->slot_blocks) (void)hipFree(b);
   }
   for (auto& e : v->ev)
     if (e) (void)hipEventDestroy(e);
@@ -428,7 +459,7 @@ void vad_upload_meta(mwx_vad_context* v, const std::vector<const float*>& ptrs,
 int vad_forward(mwx_vad_context* v, const float* const* samples, const int* n_samples, int n_clips,
                 const VadSegParams* prm, int n_prm, VadPass& ps) {
   HIPC(hipSetDevice(v->device));
-  v->timed = v->timed_trim = v->timed_chunks = false;
+  v->timed = v->timed_trim = v->timed_chunks = v->timed_stream = false;
   std::vector<size_t> stage((size_t)n_clips, 0);
   std::vector<char> on_device((size_t)n_clips, 0);
   size_t stage_floats = 0;
@@ -562,7 +593,7 @@ int vad_segments_of_probs(mwx_vad_context* v, const VadSegParams* prm, const flo
                           std::vector<mwx_vad_trimmed::Clip>& out,
                           const int64_t* caps = nullptr) {
   HIPC(hipSetDevice(v->device));
-  v->timed = v->timed_trim = v->timed_chunks = false;
+  v->timed = v->timed_trim = v->timed_chunks = v->timed_stream = false;
   VadPass ps;
   const int rc = vad_chunk_offsets(n_samples, n_clips, ps);
   if (rc != 0) return rc;
@@ -647,6 +678,171 @@ void vad_trimmed_destroy(mwx_vad_trimmed* t) {
     (void)hipFree(t->d_pcm);
   }
   delete t;
+}
+
+// ---- streams --------------------------------------------------
+constexpr int kSlotBlock = 32;           // slots per allocation of the table
+constexpr int kStreamMaxFeed = 480000;   // samples per stream per call (30 s)
+
+VadStreamSlot* vad_slot_take(mwx_vad_context* v) {
+  if (v->free_slots.empty()) {
+    VadStreamSlot* block = nullptr;
+    {
+      std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+      HIPC(hipMalloc((void**)&block, sizeof(VadStreamSlot) * kSlotBlock));
+    }
+    v->slot_blocks.push_back(block);
+    for (int i = kSlotBlock - 1; i >= 0; --i) v->free_slots.push_back(block + i);
+  }
+  VadStreamSlot* s = v->free_slots.back();
+  v->free_slots.pop_back();
+  return s;
+}
+
+void vad_stream_clear(mwx_vad_stream* s) {
+  s->n_samples = s->n_chunks = 0;
+  s->tail_n = s->par = 0;
+  s->finished = s->provisional = s->trig = false;
+  s->start = s->temp_end = s->prev_end = s->next_start = 0;
+  s->probs.clear();
+  s->max_whole = 0.0f;
+  s->seg.clear();
+}
+
+// One call over n streams. given == nullptr: counts[i] new samples at src[i]
+// go through the staging kernel, the front end, the stream recurrence and the
+// scan. given != nullptr (the test hook): counts[i] probabilities at given[i]
+// stand in for as many whole chunks and only the scan runs. The arguments have
+// been checked. The streams change only when everything has succeeded.
+int vad_stream_call(mwx_vad_context* v, mwx_vad_stream* const* streams, const float* const* src,
+                    const int* counts, int n, const float* const* given) {
+  HIPC(hipSetDevice(v->device));
+  v->timed = v->timed_trim = v->timed_chunks = v->timed_stream = false;
+  hipStream_t st = v->stream;
+  std::vector<VadStreamFeed> feeds((size_t)n);
+  std::vector<int> off((size_t)n + 1, 0), ns((size_t)n, 0);
+  std::vector<size_t> up((size_t)n, 0);  // host samples: where they go in d_pcm
+  std::vector<char> on_device((size_t)n, 0);
+  size_t up_floats = 0;
+  int max_chunks = 0;
+  for (int i = 0; i < n; ++i) {
+    const mwx_vad_stream* s = streams[i];
+    VadStreamFeed& f = feeds[i];
+    f.slot = s->slot;
+    f.src = nullptr;
+    f.par = s->par;
+    f.fresh = s->n_chunks == 0;
+    f.prm = s->prm;
+    if (given) {
+      f.n_new = f.tail_n = f.rem = 0;
+      f.n_full = counts[i];
+    } else {
+      f.n_new = counts[i];
+      f.tail_n = s->tail_n;
+      const int total = f.tail_n + f.n_new;  // < 512 + 480000
+      f.n_full = total / VAD_CHUNK;
+      f.rem = total % VAD_CHUNK;
+      ns[i] = total;
+      if (f.n_new > 0 && !(on_device[i] = vad_is_device_ptr(src[i]))) {
+        up[i] = up_floats;
+        up_floats += ((size_t)f.n_new + 3) / 4 * 4;
+      }
+    }
+    const int staged = f.n_full + (f.rem > 0 ? 1 : 0);
+    if ((long)off[i] + staged > 0x7fffffffL / VAD_CHUNK) return -3;
+    off[i + 1] = off[i] + staged;
+    max_chunks = std::max(max_chunks, staged);
+  }
+  const int total = off[n];
+  if (total == 0) return 0;  // nothing fed and no tail anywhere: nothing changes
+  float* d_pcm = up_floats ? (float*)v->d_pcm.get(up_floats * 4, st) : nullptr;
+  float* d_stage = given ? nullptr : (float*)v->d_stage.get((size_t)total * VAD_CHUNK * 4, st);
+  std::vector<const float*> ptrs((size_t)n, nullptr);
+  for (int i = 0; i < n && !given; ++i) {
+    if (feeds[i].n_new > 0) {
+      feeds[i].src = src[i];
+      if (!on_device[i]) {
+        HIPC(hipMemcpyAsync(d_pcm + up[i], src[i], (size_t)feeds[i].n_new * 4,
+                            hipMemcpyHostToDevice, st));
+        feeds[i].src = d_pcm + up[i];
+      }
+    }
+    ptrs[i] = d_stage + (size_t)off[i] * VAD_CHUNK;
+  }
+  // meta: [feeds][stage pointers][sample counts][chunk_off], one upload
+  const size_t m_feed = 0, m_ptr = m_feed + (size_t)n * sizeof(VadStreamFeed);
+  const size_t m_ns = m_ptr + (size_t)n * 8, m_off = m_ns + (size_t)n * 4;
+  const size_t m_bytes = m_off + ((size_t)n + 1) * 4;
+  static_assert(sizeof(VadStreamFeed) % 8 == 0, "meta alignment");
+  char* hm = (char*)v->h_meta.get(m_bytes);
+  char* dm = (char*)v->d_meta.get(m_bytes, st);
+  memcpy(hm + m_feed, feeds.data(), (size_t)n * sizeof(VadStreamFeed));
+  memcpy(hm + m_ptr, ptrs.data(), (size_t)n * 8);
+  memcpy(hm + m_ns, ns.data(), (size_t)n * 4);
+  memcpy(hm + m_off, off.data(), ((size_t)n + 1) * 4);
+  HIPC(hipMemcpyAsync(dm, hm, m_bytes, hipMemcpyHostToDevice, st));
+  const VadStreamFeed* d_feeds = (const VadStreamFeed*)(dm + m_feed);
+  const int* d_off = (const int*)(dm + m_off);
+  // out: [header and events, int64][probabilities, f32], one copy back
+  const size_t o_words = (size_t)VAD_STREAM_HDR * n + 3 * (size_t)total;
+  const size_t o_bytes = o_words * 8 + (size_t)total * 4;
+  char* d_out = (char*)v->d_sout.get(o_bytes, st);
+  char* h_out = (char*)v->h_sout.get(o_bytes);
+  float* d_probs = (float*)(d_out + o_words * 8);
+  if (given) {
+    float* h_in = (float*)(h_out + o_words * 8);  // (overwritten by the copy back)
+    for (int i = 0; i < n; ++i)
+      if (counts[i] > 0) memcpy(h_in + off[i], given[i], (size_t)counts[i] * 4);
+    HIPC(hipMemcpyAsync(d_probs, h_in, (size_t)total * 4, hipMemcpyHostToDevice, st));
+  } else {
+    float* d_pre = (float*)v->d_pre.get((size_t)total * VAD_GATES * 4, st);
+    HIPC(hipEventRecord(v->ev[8], st));
+    vad_stream_stage_launch(d_feeds, d_off, n, max_chunks, d_stage, st);
+    HIPC(hipEventRecord(v->ev[9], st));
+    vad_frontend_launch(v->w, (const float* const*)(dm + m_ptr), (const int*)(dm + m_ns), d_off, n,
+                        max_chunks, d_pre, st);
+    HIPC(hipEventRecord(v->ev[10], st));
+    vad_lstm_stream_launch(v->w, d_pre, d_feeds, d_off, n, d_probs, st);
+    HIPC(hipEventRecord(v->ev[11], st));
+  }
+  vad_stream_scan_launch(d_probs, d_feeds, d_off, n, (long long*)d_out, st);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(h_out, d_out, o_bytes, hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  const int64_t* words = (const int64_t*)h_out;
+  const float* probs = (const float*)(h_out + o_words * 8);
+  for (int i = 0; i < n; ++i) {  // what the scan kernel can have written
+    const int64_t* hdr = words + (size_t)VAD_STREAM_HDR * i;
+    if (hdr[0] < 0 || hdr[0] > feeds[i].n_full || hdr[6] != streams[i]->n_chunks + feeds[i].n_full)
+      return -5;
+  }
+  v->timed_stream = !given;
+  for (int i = 0; i < n; ++i) {
+    mwx_vad_stream* s = streams[i];
+    const VadStreamFeed& f = feeds[i];
+    const int64_t* hdr = words + (size_t)VAD_STREAM_HDR * i;
+    const int staged = off[i + 1] - off[i];
+    if (staged > 0) {
+      if (s->provisional) s->probs.pop_back();
+      s->probs.insert(s->probs.end(), probs + off[i], probs + off[i] + staged);
+      for (int k = 0; k < f.n_full; ++k) s->max_whole = std::max(s->max_whole, probs[off[i] + k]);
+      s->provisional = f.rem > 0;
+    }
+    s->n_samples += given ? (int64_t)VAD_CHUNK * f.n_full : (int64_t)f.n_new;
+    s->n_chunks = hdr[6];
+    if (!given) {
+      s->tail_n = f.rem;
+      s->par ^= 1;
+    }
+    const int64_t* ev = words + (size_t)VAD_STREAM_HDR * n + 3 * (size_t)off[i];
+    s->seg.insert(s->seg.end(), ev, ev + 3 * hdr[0]);
+    s->trig = hdr[1] != 0;
+    s->start = hdr[2];
+    s->temp_end = hdr[3];
+    s->prev_end = hdr[4];
+    s->next_start = hdr[5];
+  }
+  return 0;
 }
 
 }  // namespace
@@ -976,6 +1172,145 @@ int64_t mwx_test_vad_trimmed_pcm(const struct mwx_vad_trimmed* t, int clip, floa
       hipSuccess)
     return -4;
   return c.n_compact;
+}
+
+// ---- streams --------------------------------------------------------------------
+struct mwx_vad_stream* mwx_vad_stream_init(struct mwx_vad_context* vctx,
+                                           struct mwx_vad_params params) {
+  if (!vctx) return nullptr;
+  mwx::VadSegParams prm;
+  if (!mwx::vad_derive_params(params, prm)) return nullptr;
+  mwx_vad_stream* s = new mwx_vad_stream();
+  try {
+    HIPC(hipSetDevice(vctx->device));
+    s->slot = mwx::vad_slot_take(vctx);
+  } catch (const std::exception&) {
+    delete s;
+    return nullptr;
+  }
+  s->ctx = vctx;
+  s->prm = prm;
+  vctx->streams.push_back(s);
+  return s;
+}
+
+void mwx_vad_stream_free(struct mwx_vad_stream* s) {
+  if (!s) return;
+  if (mwx_vad_context* v = s->ctx) {  // every call has ended with a synchronization
+    v->free_slots.push_back(s->slot);
+    v->streams.erase(std::find(v->streams.begin(), v->streams.end(), s));
+  }
+  delete s;
+}
+
+int mwx_vad_stream_reset(struct mwx_vad_stream* s) {
+  if (!s || !s->ctx) return -1;
+  mwx::vad_stream_clear(s);  // the slot is read as new while the chunk count is 0
+  return 0;
+}
+
+int mwx_vad_stream_feed_batch(struct mwx_vad_context* vctx, struct mwx_vad_stream* const* streams,
+                              const float* const* samples, const int* n_samples, int n_streams) {
+  if (!vctx || n_streams < 0) return -1;
+  if (n_streams == 0) return 0;
+  if (!streams || !samples || !n_samples) return -1;
+  for (int i = 0; i < n_streams; ++i) {
+    const mwx_vad_stream* s = streams[i];
+    if (!s || s->ctx != vctx || s->finished) return -2;
+    if (n_samples[i] < 0 || n_samples[i] > mwx::kStreamMaxFeed) return -2;
+    if (n_samples[i] > 0 && !samples[i]) return -2;
+  }
+  std::vector<const mwx_vad_stream*> sorted(streams, streams + n_streams);
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return -2;
+  try {
+    return mwx::vad_stream_call(vctx, streams, samples, n_samples, n_streams, nullptr);
+  } catch (const std::exception&) {
+    return -4;
+  }
+}
+
+int mwx_vad_stream_finish(struct mwx_vad_stream* s) {
+  if (!s || !s->ctx || s->finished) return -1;
+  s->finished = true;
+  if (s->trig && s->n_samples - s->start > s->prm.min_speech) {
+    const int64_t e[3] = {s->start, s->n_samples, s->n_samples};
+    s->seg.insert(s->seg.end(), e, e + 3);
+  }
+  s->trig = false;
+  return 0;
+}
+
+int64_t mwx_vad_stream_n_samples(const struct mwx_vad_stream* s) { return s ? s->n_samples : 0; }
+int mwx_vad_stream_n_probs(const struct mwx_vad_stream* s) { return s ? (int)s->probs.size() : 0; }
+const float* mwx_vad_stream_probs(const struct mwx_vad_stream* s) {
+  return s && !s->probs.empty() ? s->probs.data() : nullptr;
+}
+float mwx_vad_stream_max_prob(const struct mwx_vad_stream* s) {
+  if (!s || s->probs.empty()) return 0.0f;
+  return s->provisional ? std::max(s->max_whole, s->probs.back()) : s->max_whole;
+}
+int mwx_vad_stream_n_segments(const struct mwx_vad_stream* s) {
+  return s ? (int)(s->seg.size() / 3) : 0;
+}
+int mwx_vad_stream_segment(const struct mwx_vad_stream* s, int i, int64_t* s0, int64_t* s1,
+                           int64_t* closed_at) {
+  if (!s || i < 0 || 3 * (size_t)i + 2 >= s->seg.size()) return -1;
+  if (s0) *s0 = s->seg[3 * (size_t)i];
+  if (s1) *s1 = s->seg[3 * (size_t)i + 1];
+  if (closed_at) *closed_at = s->seg[3 * (size_t)i + 2];
+  return 0;
+}
+bool mwx_vad_stream_in_speech(const struct mwx_vad_stream* s) { return s && s->trig; }
+
+int mwx_vad_stream_last_kernel_ms(struct mwx_vad_context* vctx, float* stage_ms,
+                                  float* frontend_ms, float* lstm_ms) {
+  if (!vctx || !vctx->timed_stream) return -1;
+  float a = 0.0f, b = 0.0f, c = 0.0f;
+  if (hipEventElapsedTime(&a, vctx->ev[8], vctx->ev[9]) != hipSuccess ||
+      hipEventElapsedTime(&b, vctx->ev[9], vctx->ev[10]) != hipSuccess ||
+      hipEventElapsedTime(&c, vctx->ev[10], vctx->ev[11]) != hipSuccess)
+    return -1;
+  if (stage_ms) *stage_ms = a;
+  if (frontend_ms) *frontend_ms = b;
+  if (lstm_ms) *lstm_ms = c;
+  return 0;
+}
+
+int mwx_test_vad_stream_scan(struct mwx_vad_context* vctx, const struct mwx_vad_params* params,
+                             const float* probs, int n_probs, const int* splits, int n_splits,
+                             int* n_events, int64_t* events, int64_t* state) {
+  if (!vctx || !params || n_probs < 0 || (n_probs > 0 && !probs) || n_splits < 0 ||
+      (n_splits > 0 && !splits) || !n_events || !events || !state)
+    return -1;
+  long sum = 0;
+  for (int k = 0; k < n_splits; ++k) {
+    if (splits[k] < 0 || splits[k] > 0x7fffffff / mwx::VAD_CHUNK) return -2;
+    sum += splits[k];
+  }
+  if (sum != n_probs) return -2;
+  mwx_vad_stream* s = mwx_vad_stream_init(vctx, *params);
+  if (!s) return -2;
+  int rc = 0;
+  try {
+    const float* p = probs;
+    for (int k = 0; k < n_splits && rc == 0; ++k) {
+      rc = mwx::vad_stream_call(vctx, &s, nullptr, &splits[k], 1, &p);
+      p += splits[k];
+    }
+  } catch (const std::exception&) {
+    rc = -4;
+  }
+  if (rc == 0 && s->seg.size() / 3 > (size_t)n_probs) rc = -5;
+  if (rc == 0) {
+    *n_events = (int)(s->seg.size() / 3);
+    std::copy(s->seg.begin(), s->seg.end(), events);
+    const int64_t st[6] = {s->trig ? 1 : 0, s->start, s->temp_end, s->prev_end, s->next_start,
+                           s->n_chunks};
+    std::copy(st, st + 6, state);
+  }
+  mwx_vad_stream_free(s);
+  return rc;
 }
 
 // ---- synthetic writer -------------------------------------------------------

@@ -218,6 +218,51 @@ void* mwx_stt_new_vad_trim(const char* model_dir, const char* model_filename,
   }
 }
 
+// As mwx_stt_new_vad_trim, with the streaming-VAD settings of the sessions
+// (Settings::stream_vad, stream_endpoint_silence_ms).
+void* mwx_stt_new_stream_vad(const char* model_dir, const char* model_filename,
+                             int parallel_requests, int queue_timeout_ms, int beam_size,
+                             const char* language, int vad_ms_min, int gpu_device, int max_batch,
+                             int batch_window_us, int stream_buffer_samples, int enable_vad,
+                             const char* vad_model_filename, float vad_threshold, int vad_trim,
+                             int stream_vad, int stream_endpoint_silence_ms) {
+  Settings s;
+  s.model_dir = model_dir;
+  s.model_filename = model_filename;
+  s.parallel_requests = parallel_requests;
+  s.request_queue_timeout_ms = queue_timeout_ms;
+  s.beam_size = beam_size;
+  s.language = language;
+  s.vad_ms_min_duration = vad_ms_min;
+  s.gpu_device = gpu_device;
+  s.max_batch = max_batch;
+  s.batch_window_us = batch_window_us;
+  s.stream_buffer_samples = stream_buffer_samples;
+  s.enable_vad = enable_vad != 0;
+  if (vad_model_filename) s.vad_model_filename = vad_model_filename;
+  s.vad_threshold = vad_threshold;
+  s.vad_trim = vad_trim != 0;
+  s.stream_vad = stream_vad != 0;
+  s.stream_endpoint_silence_ms = stream_endpoint_silence_ms;
+  try {
+    settings_dtw_from_env(s);
+    return new SttEngine(s);
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "SttEngine: %s\n", e.what());
+    return nullptr;
+  }
+}
+
+// Clips that went through the whole-buffer VAD gate so far.
+long mwx_stt_vad_gate_runs(void* eng) { return static_cast<SttEngine*>(eng)->vad_gate_runs(); }
+
+// Bit 0: the engine's sessions take the gate decision from a VAD stream
+// (stream_vad active); bit 1: they endpoint (stream_endpoint_silence_ms active).
+int mwx_stt_stream_vad_active(void* eng) {
+  SttEngine* e = static_cast<SttEngine*>(eng);
+  return (e->stream_vad_active() ? 1 : 0) | (e->stream_endpoint_active() ? 2 : 0);
+}
+
 // SttEngine::transcribe_batch over n_clips f32 clips at 16 kHz: a JSON list
 // with one result list per clip (as mwx_stt_transcribe_pcm16 writes one).
 // Return codes as mwx_stt_transcribe_pcm16.

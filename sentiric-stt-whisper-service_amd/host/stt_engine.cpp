@@ -31,8 +31,33 @@
 #pragma weak mwx_vad_trim_batch_chunked
 #pragma weak mwx_vad_trimmed_n_chunks
 #pragma weak mwx_full_batch_chunked
+// ... and the stream calls: without them stream_vad and
+// stream_endpoint_silence_ms are inert
+#pragma weak mwx_vad_stream_init
+#pragma weak mwx_vad_stream_free
+#pragma weak mwx_vad_stream_reset
+#pragma weak mwx_vad_stream_feed_batch
+#pragma weak mwx_vad_stream_n_probs
+#pragma weak mwx_vad_stream_probs
+#pragma weak mwx_vad_stream_max_prob
+#pragma weak mwx_vad_stream_n_segments
+#pragma weak mwx_vad_stream_segment
 
 namespace mwx_host {
+
+// One session's VAD stream. Freeing it is a call on the engine's VAD context,
+// so it takes the engine's VAD mutex.
+struct VadStreamHandle {
+  SttEngine& engine;
+  mwx_vad_stream* s;
+  VadStreamHandle(SttEngine& e, mwx_vad_stream* stream) : engine(e), s(stream) {}
+  ~VadStreamHandle() {
+    std::lock_guard<std::mutex> lock(engine.vad_mutex_);
+    mwx_vad_stream_free(s);
+  }
+  VadStreamHandle(const VadStreamHandle&) = delete;
+  VadStreamHandle& operator=(const VadStreamHandle&) = delete;
+};
 
 // The trimmed audio of one trim pass, and the object array of one
 // mwx_full_batch_trimmed call. Plain structs rather than standard containers
@@ -206,6 +231,13 @@ SttEngine::SttEngine(const Settings& settings) : settings_(settings) {
                    settings_.vad_chunk_s, settings_.vad_chunk_batch);
       settings_.vad_chunk_s = 0.0f;
     }
+    const bool stream_bound = mwx_vad_stream_init && mwx_vad_stream_free && mwx_vad_stream_reset &&
+                              mwx_vad_stream_feed_batch && mwx_vad_stream_n_probs &&
+                              mwx_vad_stream_probs && mwx_vad_stream_max_prob &&
+                              mwx_vad_stream_n_segments && mwx_vad_stream_segment &&
+                              mwx_vad_default_params;
+    stream_gate_active_ = settings_.stream_vad && vad_ctx_ && !trim_active_ && stream_bound;
+    stream_endpoint_active_ = settings_.stream_endpoint_silence_ms > 0 && vad_ctx_ && stream_bound;
   }
   const int pool = std::max(1, settings_.parallel_requests);
   if (settings_.max_batch > 1) {
@@ -533,6 +565,7 @@ std::vector<TranscriptionResult> SttEngine::collect(mwx_state* state, const std:
 
 bool SttEngine::is_speech_detected(const float* pcm, size_t n_samples) {
   if (!vad_ctx_) return true;
+  vad_gate_runs_++;
   std::lock_guard<std::mutex> lock(vad_mutex_);
   if (!mwx_vad_detect_speech(vad_ctx_, pcm, static_cast<int>(n_samples))) return true;
   const int n = mwx_vad_n_probs(vad_ctx_);
@@ -581,6 +614,66 @@ std::vector<TranscriptionResult> SttEngine::transcribe(const std::vector<float>&
                                                        int input_sample_rate,
                                                        const RequestOptions& options,
                                                        PerformanceMetrics* out_metrics) {
+  return transcribe_impl(pcmf32, input_sample_rate, options, out_metrics, nullptr);
+}
+
+std::vector<TranscriptionResult> SttEngine::transcribe_pcm16_gated(
+    const std::vector<int16_t>& pcm16, const RequestOptions& options, bool speech,
+    PerformanceMetrics* out_metrics) {
+  std::vector<float> f(pcm16.size());
+  for (size_t i = 0; i < pcm16.size(); ++i) f[i] = static_cast<float>(pcm16[i]) / 32768.0f;
+  return transcribe_impl(f, 16000, options, out_metrics, &speech);
+}
+
+// ---- VAD streams of the sessions --------------------------------------------
+std::shared_ptr<VadStreamHandle> SttEngine::vad_stream_open() {
+  if (!stream_gate_active_ && !stream_endpoint_active_) return nullptr;
+  mwx_vad_params vp = mwx_vad_default_params();
+  vp.threshold = settings_.vad_threshold;
+  if (stream_endpoint_active_) vp.min_silence_duration_ms = settings_.stream_endpoint_silence_ms;
+  std::lock_guard<std::mutex> lock(vad_mutex_);
+  mwx_vad_stream* s = mwx_vad_stream_init(vad_ctx_, vp);
+  if (!s) return nullptr;
+  return std::make_shared<VadStreamHandle>(*this, s);
+}
+
+bool SttEngine::vad_stream_feed(VadStreamHandle& h, const float* pcm, size_t n) {
+  constexpr size_t kMaxFeed = 480000;  // mwx_vad_stream_feed_batch's limit per call
+  for (size_t at = 0; at < n; at += kMaxFeed) {
+    const float* p = pcm + at;
+    const int k = static_cast<int>(std::min(kMaxFeed, n - at));
+    std::lock_guard<std::mutex> lock(vad_mutex_);
+    if (mwx_vad_stream_feed_batch(vad_ctx_, &h.s, &p, &k, 1) != 0) return false;
+  }
+  return true;
+}
+
+bool SttEngine::vad_stream_reset(VadStreamHandle& h) {
+  std::lock_guard<std::mutex> lock(vad_mutex_);
+  return mwx_vad_stream_reset(h.s) == 0;
+}
+
+bool SttEngine::vad_stream_speech(const VadStreamHandle& h, long n_chunks) const {
+  if (n_chunks < 0) return mwx_vad_stream_max_prob(h.s) >= settings_.vad_threshold;
+  const long n = std::min<long>(n_chunks, mwx_vad_stream_n_probs(h.s));
+  const float* probs = mwx_vad_stream_probs(h.s);
+  for (long i = 0; i < n; ++i)
+    if (probs[i] >= settings_.vad_threshold) return true;
+  return false;
+}
+
+int64_t SttEngine::vad_stream_last_closed_at(const VadStreamHandle& h) const {
+  const int n = mwx_vad_stream_n_segments(h.s);
+  int64_t at = 0;
+  if (n <= 0 || mwx_vad_stream_segment(h.s, n - 1, nullptr, nullptr, &at) != 0) return 0;
+  return at;
+}
+
+std::vector<TranscriptionResult> SttEngine::transcribe_impl(const std::vector<float>& pcmf32,
+                                                            int input_sample_rate,
+                                                            const RequestOptions& options,
+                                                            PerformanceMetrics* out_metrics,
+                                                            const bool* gate) {
   const auto t_start = std::chrono::steady_clock::now();
   if (!ctx_) return {};
   if (options.should_abort && options.should_abort()) return {};
@@ -609,7 +702,8 @@ std::vector<TranscriptionResult> SttEngine::transcribe(const std::vector<float>&
     trimmed = trim_clips(&p, &n, 1);
     speech = !trimmed || mwx_vad_trimmed_n_segments(trimmed->t, 0) != 0;
   } else if (settings_.enable_vad) {
-    speech = is_speech_detected(pcm.data(), pcm_size);
+    // (a session with a VAD stream has the decision already)
+    speech = gate ? *gate : is_speech_detected(pcm.data(), pcm_size);
   }
   if (!speech) {
     if (out_metrics)
@@ -721,6 +815,7 @@ std::vector<std::vector<TranscriptionResult>> SttEngine::transcribe_batch(
     std::vector<float> probs(static_cast<size_t>(std::max(total, 1)));
     int rc = 0;
     if (!gated.empty()) {
+      vad_gate_runs_ += static_cast<long>(gated.size());
       std::lock_guard<std::mutex> lock(vad_mutex_);
       rc = mwx_vad_detect_speech_batch(vad_ctx_, vptrs.data(), vlens.data(),
                                        static_cast<int>(gated.size()), probs.data(), voff.data());

@@ -18,7 +18,9 @@
 // The gate's decision rule is this engine's own (deviation D6): any
 // chunk probability >= Settings::vad_threshold. Settings::vad_trim (off by
 // default) replaces the gate by silence trimming: mwx_vad_trim_batch +
-// mwx_full_batch_trimmed (deviation D7).
+// mwx_full_batch_trimmed (deviation D7). Settings::stream_vad and
+// stream_endpoint_silence_ms (off by default) give the stream sessions a VAD
+// that is fed incrementally (mwx_vad_stream_*; deviation D11).
 #pragma once
 
 #include <atomic>
@@ -110,6 +112,22 @@ struct Settings {
   // sessions do not chunk.
   float vad_chunk_s = 0.0f;
   int vad_chunk_batch = 32;
+  // Streaming VAD for StreamSession (INTEGRATION.md "Streaming"),
+  // both off by default and inert without a loaded VAD model or against a
+  // library that lacks the mwx_vad_stream_* calls.
+  // stream_vad: with the gate path active (enable_vad, a VAD model, vad_trim not
+  // active) a session feeds every sample it buffers to a VAD stream of its own
+  // and hands the gate decision (max probability >= vad_threshold: rule D6 on
+  // the buffer, bit for bit) to its transcriptions instead of running the gate
+  // over the whole buffer again for every partial. The events do not change.
+  bool stream_vad = false;
+  // stream_endpoint_silence_ms = S > 0: server-side endpointing. The session's
+  // VAD stream runs the segment rule with threshold = vad_threshold and
+  // min_silence_duration_ms = S (the other mwx_vad_params at their defaults);
+  // when a feed closes a speech segment the buffer up to the end of the chunk
+  // that closed it is transcribed and finalized as the client's empty chunk
+  // finalizes it, and the buffer goes on with the rest.
+  int stream_endpoint_silence_ms = 0;
 };
 
 // Reads the DTW settings from the environment, as the service reads its other
@@ -123,6 +141,9 @@ void settings_dtw_from_env(Settings& s);
 
 // Owner of one mwx_vad_trimmed (vad_trim; defined in stt_engine.cpp).
 struct TrimmedAudio;
+// Owner of one mwx_vad_stream (stream_vad / stream_endpoint_silence_ms; defined
+// in stt_engine.cpp). Must not outlive its engine.
+struct VadStreamHandle;
 
 struct TokenData {
   std::string text;
@@ -278,6 +299,34 @@ class SttEngine {
   // Batches run by the request batcher so far (max_batch > 1).
   long batches_run() const { return batches_run_.load(); }
 
+  // ---- streaming VAD (Settings::stream_vad / stream_endpoint_silence_ms) ----
+  // Whether a StreamSession of this engine takes its gate decisions from a VAD
+  // stream / endpoints on the server side.
+  bool stream_vad_active() const { return stream_gate_active_; }
+  bool stream_endpoint_active() const { return stream_endpoint_active_; }
+  // Clips that went through the whole-buffer VAD gate so far (is_speech_detected
+  // and transcribe_batch's batched gate pass).
+  long vad_gate_runs() const { return vad_gate_runs_.load(); }
+  // transcribe_pcm16 at 16 kHz with the gate's decision supplied by the caller
+  // (`speech`) wherever transcribe() would run the gate over the clip.
+  std::vector<TranscriptionResult> transcribe_pcm16_gated(const std::vector<int16_t>& pcm16,
+                                                          const RequestOptions& options,
+                                                          bool speech,
+                                                          PerformanceMetrics* out_metrics = nullptr);
+  // A VAD stream for one session; null when neither setting is active or the
+  // library refuses. Every call below takes the VAD mutex for one
+  // mwx_vad_stream_* call (n = 1); false = the call failed.
+  std::shared_ptr<VadStreamHandle> vad_stream_open();
+  bool vad_stream_feed(VadStreamHandle& h, const float* pcm, size_t n);
+  bool vad_stream_reset(VadStreamHandle& h);
+  // The two queries below read what the stream's last call left on the host
+  // and take no lock: a stream is used by its one session.
+  // Rule D6 over the first n_chunks probabilities of the stream (< 0: all of
+  // them, the provisional one of a partial last chunk included).
+  bool vad_stream_speech(const VadStreamHandle& h, long n_chunks = -1) const;
+  // closed_at of the last raw segment the stream has closed; 0 when none.
+  int64_t vad_stream_last_closed_at(const VadStreamHandle& h) const;
+
  private:
   // ---- dynamic request batching (Settings::max_batch > 1) ----
   struct Pending {
@@ -321,6 +370,16 @@ class SttEngine {
                                               int n_clips);
   bool trim_active_ = false;  // vad_trim, a VAD context and a library that has the calls
   bool chunk_bound_ = false;  // the library has the chunked calls
+  bool stream_gate_active_ = false;      // stream_vad, the gate path and the stream calls
+  bool stream_endpoint_active_ = false;  // stream_endpoint_silence_ms, a VAD context, the calls
+  std::atomic<long> vad_gate_runs_{0};
+  friend struct VadStreamHandle;
+  // transcribe() with the gate decision optionally supplied (gate != nullptr)
+  std::vector<TranscriptionResult> transcribe_impl(const std::vector<float>& pcmf32,
+                                                   int input_sample_rate,
+                                                   const RequestOptions& options,
+                                                   PerformanceMetrics* out_metrics,
+                                                   const bool* gate);
   // the chunk batch of the engine call over trimmed audio: > 0 with chunking
   // active (mwx_full_batch_chunked), 0 for mwx_full_batch_trimmed
   int chunk_batch() const { return chunk_active() ? settings_.vad_chunk_batch : 0; }

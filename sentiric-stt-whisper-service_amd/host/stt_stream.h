@@ -21,6 +21,21 @@
 //    with all affect fields and its words (token text, t0 / 100, t1 / 100, p),
 //    then the buffer restarts (:150-190).
 //
+// Engine extensions, both off by default (the reference has
+// neither):
+//  * Settings::stream_vad: the session feeds every sample it buffers
+//    (s / 32768.0f, as transcribe_pcm16 converts) to a VAD stream of its own,
+//    restarted whenever the buffer restarts, and its transcriptions take the
+//    gate's decision from it. The events are those of the whole-buffer gate.
+//  * Settings::stream_endpoint_silence_ms = S > 0, server-side endpointing:
+//    after a chunk whose samples close at least one raw speech segment of the
+//    VAD stream (rule D7 with min_silence_duration_ms = S), cut = the last
+//    one's closed_at; buffer_[0, cut) is transcribed and its non-empty
+//    segments become final events exactly as the empty chunk finalizes them;
+//    the buffer becomes buffer_[cut:], the VAD stream restarts and is fed the
+//    remainder, and the same test runs again on what that closes. Then the
+//    partial cadence test runs on the new buffer.
+//
 // GPU-side, concurrent sessions of an engine built with Settings::max_batch > 1
 // have their re-transcriptions gathered into shared mwx_full_batch calls by
 // the engine's request batcher: many live streams, one decode loop.
@@ -74,7 +89,18 @@ class StreamSession {
   static constexpr size_t kMaxBufferSamples = 16000 * 30;  // src/grpc_server.cpp:132
 
  private:
+  // the engine's transcription of `pcm` = buffer_[0, pcm.size()): through the
+  // gate decision of the VAD stream when the session has one for that
+  std::vector<TranscriptionResult> transcribe(const std::vector<int16_t>& pcm,
+                                              SttEngine::PerformanceMetrics* perf);
+  void vad_feed(size_t from);    // buffer_[from, end) -> the VAD stream
+  void restart_buffer(size_t keep_from);  // buffer_ = buffer_[keep_from:], VAD stream anew
+  void drop_vad();               // a failed VAD stream call: the session goes on as without one
+
   SttEngine& engine_;
+  std::shared_ptr<VadStreamHandle> vad_;  // Settings::stream_vad / stream_endpoint_silence_ms
+  bool gate_from_stream_ = false;
+  bool endpoint_ = false;
   std::vector<int16_t> buffer_;
   size_t last_processed_ = 0;
   size_t step_;  // Settings::stream_buffer_samples

@@ -397,6 +397,35 @@ def lib() -> C.CDLL:
     L.mwx_test_vad_chunks.restype = C.c_int
     L.mwx_test_vad_chunks.argtypes = [P, C.POINTER(VadParams), i64p, fpp, ip, ip, C.c_int, ip,
                                       i64p, ip]
+    L.mwx_vad_stream_init.restype = P
+    L.mwx_vad_stream_init.argtypes = [P, VadParams]
+    L.mwx_vad_stream_free.restype = None
+    L.mwx_vad_stream_free.argtypes = [P]
+    L.mwx_vad_stream_reset.restype = C.c_int
+    L.mwx_vad_stream_reset.argtypes = [P]
+    L.mwx_vad_stream_feed_batch.restype = C.c_int
+    L.mwx_vad_stream_feed_batch.argtypes = [P, C.POINTER(P), C.POINTER(C.c_void_p), ip, C.c_int]
+    L.mwx_vad_stream_finish.restype = C.c_int
+    L.mwx_vad_stream_finish.argtypes = [P]
+    L.mwx_vad_stream_n_samples.restype = C.c_int64
+    L.mwx_vad_stream_n_samples.argtypes = [P]
+    L.mwx_vad_stream_n_probs.restype = C.c_int
+    L.mwx_vad_stream_n_probs.argtypes = [P]
+    L.mwx_vad_stream_probs.restype = fpp
+    L.mwx_vad_stream_probs.argtypes = [P]
+    L.mwx_vad_stream_max_prob.restype = C.c_float
+    L.mwx_vad_stream_max_prob.argtypes = [P]
+    L.mwx_vad_stream_n_segments.restype = C.c_int
+    L.mwx_vad_stream_n_segments.argtypes = [P]
+    L.mwx_vad_stream_segment.restype = C.c_int
+    L.mwx_vad_stream_segment.argtypes = [P, C.c_int, i64p, i64p, i64p]
+    L.mwx_vad_stream_in_speech.restype = C.c_bool
+    L.mwx_vad_stream_in_speech.argtypes = [P]
+    L.mwx_vad_stream_last_kernel_ms.restype = C.c_int
+    L.mwx_vad_stream_last_kernel_ms.argtypes = [P, fpp, fpp, fpp]
+    L.mwx_test_vad_stream_scan.restype = C.c_int
+    L.mwx_test_vad_stream_scan.argtypes = [P, C.POINTER(VadParams), fpp, C.c_int, ip, C.c_int, ip,
+                                           i64p, i64p]
     _lib = L
     return L
 
@@ -1461,6 +1490,38 @@ class VadContext:
             raise RuntimeError("mwx_vad_last_trim_kernel_ms: no timed call")
         return a.value, b.value
 
+    def stream(self, params: Optional[VadParams] = None) -> "VadStream":
+        """mwx_vad_stream_init: a stream of this context."""
+        return VadStream(self, params)
+
+    def last_stream_kernel_ms(self):
+        """(staging, front end, recurrence + head) device milliseconds of the
+        last VadStream.feed_batch."""
+        a, b, c = C.c_float(), C.c_float(), C.c_float()
+        if lib().mwx_vad_stream_last_kernel_ms(self.vctx, C.byref(a), C.byref(b),
+                                               C.byref(c)) != 0:
+            raise RuntimeError("mwx_vad_stream_last_kernel_ms: no timed call")
+        return a.value, b.value, c.value
+
+    def test_stream_scan(self, probs: np.ndarray, splits: Sequence[int], params: VadParams):
+        """mwx_test_vad_stream_scan: the online scan over given probabilities fed
+        splits[k] chunks at a time. ([(s0, s1, closed_at)], (trig, start,
+        temp_end, prev_end, next_start, chunk count))."""
+        p = np.ascontiguousarray(probs, np.float32)
+        flat = np.concatenate([p, np.zeros(1, np.float32)])
+        sp = np.ascontiguousarray(splits, np.int32)
+        n_ev = C.c_int()
+        ev = np.zeros(3 * max(1, len(p)), np.int64)
+        st = np.zeros(6, np.int64)
+        ip, i64p = C.POINTER(C.c_int), C.POINTER(C.c_int64)
+        rc = lib().mwx_test_vad_stream_scan(self.vctx, C.byref(params), fptr(flat), len(p),
+                                            sp.ctypes.data_as(ip), len(sp), C.byref(n_ev),
+                                            ev.ctypes.data_as(i64p), st.ctypes.data_as(i64p))
+        if rc != 0:
+            raise RuntimeError(f"mwx_test_vad_stream_scan failed ({rc})")
+        return ([tuple(int(v) for v in ev[3 * k:3 * k + 3]) for k in range(n_ev.value)],
+                tuple(int(v) for v in st))
+
     def test_segments(self, probs: Sequence[np.ndarray], n_samples: Sequence[int],
                       params: Sequence[VadParams]):
         """mwx_test_vad_segments: vad_segments_kernel over given probabilities.
@@ -1489,6 +1550,90 @@ class VadContext:
             out.append(([tuple(int(v) for v in seg[2 * (o + k):2 * (o + k) + 2]) for k in range(m)],
                         [tuple(int(v) for v in pcs[3 * (o + k):3 * (o + k) + 3]) for k in range(m)],
                         int(clen[b])))
+        return out
+
+
+class VadStream:
+    """mwx_vad_stream: a VAD that is fed a piece at a time. Its
+    probabilities are, bit for bit, VadContext.detect of everything fed since
+    the last reset; its segments are rule D7's raw (unpadded) segments. Belongs
+    to its VadContext (one call at a time per context); free it first."""
+
+    def __init__(self, vad: "VadContext", params: Optional[VadParams] = None):
+        self.vad = vad
+        self.s = lib().mwx_vad_stream_init(vad.vctx, params or vad_params())
+        if not self.s:
+            raise RuntimeError("mwx_vad_stream_init failed")
+
+    def free(self):
+        if self.s:
+            lib().mwx_vad_stream_free(self.s)
+            self.s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+    def reset(self) -> None:
+        if lib().mwx_vad_stream_reset(self.s) != 0:
+            raise RuntimeError("mwx_vad_stream_reset failed")
+
+    def feed(self, pcm) -> None:
+        """mwx_vad_stream_feed_batch with this stream alone."""
+        VadStream.feed_batch([self], [pcm])
+
+    @staticmethod
+    def feed_batch(streams: Sequence["VadStream"], pcms) -> None:
+        """mwx_vad_stream_feed_batch: pcms[i] (numpy or DevicePCM, may be empty)
+        is appended to streams[i], all in one pass. Streams of one context."""
+        n = len(streams)
+        if n == 0:
+            return
+        clips = [VadContext._clip(p) for p in pcms]
+        hs = (C.c_void_p * n)(*[s.s for s in streams])
+        ptrs = (C.c_void_p * n)(*[c[1] for c in clips])
+        lens = (C.c_int * n)(*[c[2] for c in clips])
+        rc = lib().mwx_vad_stream_feed_batch(streams[0].vad.vctx, hs, ptrs, lens, n)
+        if rc != 0:
+            raise RuntimeError(f"mwx_vad_stream_feed_batch failed ({rc})")
+
+    def finish(self) -> None:
+        if lib().mwx_vad_stream_finish(self.s) != 0:
+            raise RuntimeError("mwx_vad_stream_finish failed")
+
+    @property
+    def n_samples(self) -> int:
+        return lib().mwx_vad_stream_n_samples(self.s)
+
+    @property
+    def n_probs(self) -> int:
+        return lib().mwx_vad_stream_n_probs(self.s)
+
+    def probs(self) -> np.ndarray:
+        k = self.n_probs
+        if k == 0:
+            return np.empty(0, np.float32)
+        return np.ctypeslib.as_array(lib().mwx_vad_stream_probs(self.s), shape=(k,)).copy()
+
+    @property
+    def max_prob(self) -> float:
+        return lib().mwx_vad_stream_max_prob(self.s)
+
+    @property
+    def in_speech(self) -> bool:
+        return bool(lib().mwx_vad_stream_in_speech(self.s))
+
+    def segments(self) -> List[tuple]:
+        """[(s0, s1, closed_at), ...]: the raw segments closed since reset."""
+        L = lib()
+        out = []
+        for i in range(L.mwx_vad_stream_n_segments(self.s)):
+            a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+            if L.mwx_vad_stream_segment(self.s, i, C.byref(a), C.byref(b), C.byref(c)) != 0:
+                raise RuntimeError("mwx_vad_stream_segment failed")
+            out.append((a.value, b.value, c.value))
         return out
 
 
