@@ -383,6 +383,46 @@ int mwx_test_vad_stream_scan(struct mwx_vad_context* vctx, const struct mwx_vad_
                              const float* probs, int n_probs, const int* splits, int n_splits,
                              int* n_events, int64_t* events, int64_t* state);
 
+/* --- logits processing on given data (tests/test_gpu_logits_kernels.py) ---- */
+
+/* RowCtl (csrc/kernels.h) of one row, as plain ints plus the temperature. */
+struct mwx_test_logits_ctl {
+  int active, sample, is_initial, last_ts, penult_ts, has_ts, seek_delta, want_probs, want_nosp;
+  float temperature;
+};
+/* LogitsConst (csrc/kernels.h). */
+struct mwx_test_logits_const {
+  int n_vocab, eot, beg, space_id, suppress_blank, max_initial_tid, nosp_id;
+};
+/* TokOut (csrc/kernels.h) without its pad word. */
+struct mwx_test_logits_out {
+  int id, tid;
+  float p, plog, pt, ptsum, nosp;
+};
+
+/* One logits_process(..., pick = true) call (lp_filter_kernel, lp_probs_kernel,
+ * lp_pick_kernel) on R rows of V raw logits [R][V], the static mask smask [V]
+ * (< 0: suppressed), ctl [R] and *lc. Out: flt, probs, logprobs [R][V] and
+ * out [R]. The hook owns every device buffer (probs and logprobs included).
+ * Every output starts as all-ones bits (NaN; id = tid = -1), so a row whose
+ * ctl has active = 0 or sample = 0, and probs / logprobs of a row without
+ * want_probs, come back as such. Each device output, the chunk records
+ * included, lies between two guard bands of sentinel words.
+ * Returns 0; -1 without a launch unless 1 <= R <= 256, 1 <= V == lc->n_vocab,
+ * eot, space_id and nosp_id in [0, V), beg in [0, V] and every seek_delta >= 0;
+ * -4 (no launch) for V > LP_G * LP_CHUNK = 53248; -2 on a device error; -3 if
+ * a launch changed a guard band. */
+int mwx_test_logits_process(struct mwx_context* ctx, int R, int V, const float* logits,
+                            const float* smask, const struct mwx_test_logits_ctl* ctl,
+                            const struct mwx_test_logits_const* lc, float* flt, float* probs,
+                            float* logprobs, struct mwx_test_logits_out* out);
+
+/* The engine's own LogitsConst and static suppression mask for a call with
+ * *params (the functions the decode driver calls; host code, no device work):
+ * *lc and smask [n_vocab] (0 or -inf). Returns 0, or -1 on a null argument. */
+int mwx_test_logits_setup(struct mwx_context* ctx, const struct mwx_full_params* params,
+                          struct mwx_test_logits_const* lc, float* smask);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,12 @@ struct ModelFile {
   std::map<std::string, FileTensor> tensors;
 };
 
+// The largest n_vocab the logits-processing kernels cover (kernels.h: LP_G *
+// LP_CHUNK, checked equal in engine.cpp). A larger model is refused when its
+// file is read and when a context is created.
+constexpr int kMaxVocab = 53248;
+bool vocab_fits(int n_vocab);  // logs the refusal
+
 // Parses a whisper ggml .bin file. Returns false (and logs) on any error.
 bool read_model_file(const char* path, ModelFile& mf);
 

@@ -1570,6 +1570,10 @@ struct mwx_context* mwx_init_from_file_with_params(const char* path,
     HIPC(hipSetDevice(params.gpu_device));
     mwx::ModelFile mf;
     if (!mwx::read_model_file(path, mf)) return nullptr;
+    // (read_model_file has just made this very check, so this one cannot fire
+    // today; it stays so that a context never holds a vocabulary the logits
+    // kernels' LP_G x LP_CHUNK split does not cover, however its Hparams come)
+    if (!mwx::vocab_fits(mf.hp.n_vocab)) return nullptr;
     auto* ctx = new mwx_context();
     Context& C = ctx->c;
     C.device = params.gpu_device;
@@ -3368,6 +3372,107 @@ extern "C" int mwx_test_gelu_table(struct mwx_context* ctx, uint16_t* out) {
   } catch (...) {
     return -2;
   }
+}
+
+// ---------------------------------------------------------------------------
+// Logits processing on given data (mwx_test_logits_process / _setup)
+// ---------------------------------------------------------------------------
+extern "C" int mwx_test_logits_process(struct mwx_context* ctx, int R, int V, const float* logits,
+                                       const float* smask,
+                                       const struct mwx_test_logits_ctl* ctl,
+                                       const struct mwx_test_logits_const* lc, float* flt,
+                                       float* probs, float* logprobs,
+                                       struct mwx_test_logits_out* out) {
+  if (!ctx || !logits || !smask || !ctl || !lc || !flt || !probs || !logprobs || !out) return -1;
+  if (R < 1 || R > 256 || V < 1 || lc->n_vocab != V) return -1;
+  auto in_v = [&](int i) { return i >= 0 && i < V; };
+  if (!in_v(lc->eot) || !in_v(lc->space_id) || !in_v(lc->nosp_id) || lc->beg < 0 || lc->beg > V)
+    return -1;
+  for (int r = 0; r < R; ++r)
+    if (ctl[r].seek_delta < 0) return -1;
+  if (V > mwx::LP_G * mwx::LP_CHUNK) return -4;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    mwx::LogitsConst C;
+    C.n_vocab = V;
+    C.eot = lc->eot;
+    C.beg = lc->beg;
+    C.space_id = lc->space_id;
+    C.suppress_blank = lc->suppress_blank;
+    C.max_initial_tid = lc->max_initial_tid;
+    C.nosp_id = lc->nosp_id;
+    std::vector<mwx::RowCtl> hc(R);
+    for (int r = 0; r < R; ++r) {
+      mwx::RowCtl& k = hc[r];
+      memset(&k, 0, sizeof(k));
+      k.active = ctl[r].active;
+      k.sample = ctl[r].sample;
+      k.is_initial = ctl[r].is_initial;
+      k.last_ts = ctl[r].last_ts;
+      k.penult_ts = ctl[r].penult_ts;
+      k.has_ts = ctl[r].has_ts;
+      k.seek_delta = ctl[r].seek_delta;
+      k.want_probs = ctl[r].want_probs;
+      k.temperature = ctl[r].temperature;
+      k.want_nosp = ctl[r].want_nosp;
+    }
+    const size_t rv = (size_t)R * V * 4;
+    DevScratch m;
+    float* dl = (float*)m.get(rv);
+    float* dm = (float*)m.get((size_t)V * 4);
+    mwx::RowCtl* dc = (mwx::RowCtl*)m.get((size_t)R * sizeof(mwx::RowCtl));
+    HIPC(hipMemcpy(dl, logits, rv, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dm, smask, (size_t)V * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dc, hc.data(), (size_t)R * sizeof(mwx::RowCtl), hipMemcpyHostToDevice));
+    GuardedBuf gf, gp, gl, go, gparts, gres;
+    mwx::LPScratch ws;
+    ws.flt = (float*)gf.make(m, rv, nullptr);
+    ws.parts = (mwx::LPPart*)gparts.make(m, (size_t)R * mwx::LP_G * sizeof(mwx::LPPart), nullptr);
+    ws.res = (mwx::LPRes*)gres.make(m, (size_t)R * mwx::LP_G * sizeof(mwx::LPRes), nullptr);
+    float* dp = (float*)gp.make(m, rv, nullptr);
+    float* dlp = (float*)gl.make(m, rv, nullptr);
+    mwx::TokOut* dout = (mwx::TokOut*)go.make(m, (size_t)R * sizeof(mwx::TokOut), nullptr);
+    mwx::logits_process(dl, dm, dc, dout, dp, dlp, C, R, ws, nullptr, true);
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    std::vector<mwx::TokOut> ho(R);
+    std::vector<uint8_t> hparts(gparts.bytes), hres(gres.bytes);
+    bool ok = gf.take(flt);
+    ok = gp.take(probs) && ok;
+    ok = gl.take(logprobs) && ok;
+    ok = go.take(ho.data()) && ok;
+    ok = gparts.take(hparts.data()) && ok;
+    ok = gres.take(hres.data()) && ok;
+    if (!ok) return -3;
+    for (int r = 0; r < R; ++r) {
+      out[r].id = ho[r].id;
+      out[r].tid = ho[r].tid;
+      out[r].p = ho[r].p;
+      out[r].plog = ho[r].plog;
+      out[r].pt = ho[r].pt;
+      out[r].ptsum = ho[r].ptsum;
+      out[r].nosp = ho[r].nosp;
+    }
+    return 0;
+  } catch (...) {
+    return -2;
+  }
+}
+
+extern "C" int mwx_test_logits_setup(struct mwx_context* ctx, const struct mwx_full_params* params,
+                                     struct mwx_test_logits_const* lc, float* smask) {
+  if (!ctx || !params || !lc || !smask) return -1;
+  const mwx::LogitsConst C = mwx::logits_const(ctx->c, *params);
+  lc->n_vocab = C.n_vocab;
+  lc->eot = C.eot;
+  lc->beg = C.beg;
+  lc->space_id = C.space_id;
+  lc->suppress_blank = C.suppress_blank;
+  lc->max_initial_tid = C.max_initial_tid;
+  lc->nosp_id = C.nosp_id;
+  const std::vector<float> m = mwx::static_mask(ctx->c, *params);
+  memcpy(smask, m.data(), m.size() * sizeof(float));
+  return 0;
 }
 
 // ---------------------------------------------------------------------------

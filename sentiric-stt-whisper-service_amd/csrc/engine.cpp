@@ -832,6 +832,54 @@ struct Row {
   std::vector<mwx_token_data> tokens;
 };
 
+static_assert(kMaxVocab == LP_G * LP_CHUNK, "common.h kMaxVocab is the chunks' coverage");
+
+// The logits-processing constants of a call (Driver, mwx_test_logits_setup)
+static LogitsConst logits_const(const Context& C, const mwx_full_params& P) {
+  LogitsConst LC;
+  LC.n_vocab = C.hp.n_vocab;
+  LC.eot = C.vocab.token_eot;
+  LC.beg = C.vocab.token_beg;
+  LC.space_id = C.space_id;
+  LC.suppress_blank = P.suppress_blank ? 1 : 0;
+  LC.nosp_id = C.vocab.token_nosp;
+  if (P.max_initial_ts > 0.0f) {
+    const float precision = float(MWX_CHUNK_SIZE) / C.hp.n_audio_ctx;
+    LC.max_initial_tid = C.vocab.token_beg + (int)std::round(P.max_initial_ts / precision);
+  } else {
+    LC.max_initial_tid = -1;
+  }
+  return LC;
+}
+
+// The static suppression mask of a call's params (0 or -inf per id)
+static std::vector<float> static_mask(const Context& C, const mwx_full_params& P) {
+  const int V = C.hp.n_vocab;
+  std::vector<float> m(V, 0.0f);
+  const Vocab& vb = C.vocab;
+  const float NI = -INFINITY;
+  m[vb.token_not] = NI;
+  if (P.no_timestamps)
+    for (int i = vb.token_beg; i < V; ++i) m[i] = NI;
+  m[vb.token_sot] = NI;
+  m[vb.token_nosp] = NI;
+  if (!P.tdrz_enable) m[vb.token_solm] = NI;
+  m[vb.token_translate] = NI;
+  m[vb.token_transcribe] = NI;
+  m[vb.token_prev] = NI;
+  for (int i = 0; i <= lang_max_id(); ++i) {
+    const int tok = vb.token_sot + 1 + i;
+    if (tok < V) m[tok] = NI;
+  }
+  if (P.suppress_nst)
+    for (int id : C.nst_ids) m[id] = NI;
+  if (P.bench_fixed_steps > 0) {
+    m[vb.token_eot] = NI;
+    for (int i = vb.token_beg; i < V; ++i) m[i] = NI;
+  }
+  return m;
+}
+
 template <typename T>
 struct Driver {
   Context& C;
@@ -877,18 +925,7 @@ struct Driver {
     L_dec = hp.n_text_layer;
     V = hp.n_vocab;
     Tctx = hp.n_text_ctx;
-    LC.n_vocab = V;
-    LC.eot = C.vocab.token_eot;
-    LC.beg = C.vocab.token_beg;
-    LC.space_id = C.space_id;
-    LC.suppress_blank = P.suppress_blank ? 1 : 0;
-    LC.nosp_id = C.vocab.token_nosp;
-    if (P.max_initial_ts > 0.0f) {
-      const float precision = float(MWX_CHUNK_SIZE) / hp.n_audio_ctx;
-      LC.max_initial_tid = C.vocab.token_beg + (int)std::round(P.max_initial_ts / precision);
-    } else {
-      LC.max_initial_tid = -1;
-    }
+    LC = logits_const(C, P);
   }
 
   const T* Wt(const void* p) const { return (const T*)p; }
@@ -898,28 +935,7 @@ struct Driver {
 
   // static suppression mask for this call's params
   void build_static_mask() {
-    std::vector<float> m(V, 0.0f);
-    const Vocab& vb = C.vocab;
-    const float NI = -INFINITY;
-    m[vb.token_not] = NI;
-    if (P.no_timestamps)
-      for (int i = vb.token_beg; i < V; ++i) m[i] = NI;
-    m[vb.token_sot] = NI;
-    m[vb.token_nosp] = NI;
-    if (!P.tdrz_enable) m[vb.token_solm] = NI;
-    m[vb.token_translate] = NI;
-    m[vb.token_transcribe] = NI;
-    m[vb.token_prev] = NI;
-    for (int i = 0; i <= lang_max_id(); ++i) {
-      const int tok = vb.token_sot + 1 + i;
-      if (tok < V) m[tok] = NI;
-    }
-    if (P.suppress_nst)
-      for (int id : C.nst_ids) m[id] = NI;
-    if (P.bench_fixed_steps > 0) {
-      m[vb.token_eot] = NI;
-      for (int i = vb.token_beg; i < V; ++i) m[i] = NI;
-    }
+    const std::vector<float> m = static_mask(C, P);
     float* dm = (float*)S.smask.get((size_t)V * 4);
     HIPC(hipMemcpyAsync(dm, m.data(), (size_t)V * 4, hipMemcpyHostToDevice, st));
   }

@@ -426,9 +426,12 @@ void row_advance(RowRun* run, int* run_step, const int* prompt, int* stepin, Row
                  const PickIn& pk, hipStream_t st);
 
 // Logits processing is split over LP_G chunks of LP_CHUNK vocabulary entries
-// per row (LP_G * LP_CHUNK >= n_vocab for every Whisper vocabulary).
+// per row (LP_G * LP_CHUNK >= n_vocab for every Whisper vocabulary). An id
+// past LP_G * LP_CHUNK would belong to no chunk: the loader and context
+// creation refuse such a model (common.h kMaxVocab).
 constexpr int LP_G = 16;
 constexpr int LP_CHUNK = 3328;  // 13 x 256
+static_assert(LP_G * LP_CHUNK >= 51866, "the chunks must cover the largest Whisper vocabulary");
 struct LPPart {  // per-chunk statistics of the filtered (and raw) logits
   float m, s, mtext, mts, sts, rm, rs, pad;
 };

@@ -240,6 +240,13 @@ static void finalize_vocab(Vocab& vocab, int32_t n_vocab_file) {
   }
 }
 
+bool vocab_fits(int n_vocab) {
+  if (n_vocab >= 0 && n_vocab <= kMaxVocab) return true;
+  MWX_LOG_ERROR("mwx: n_vocab %d is outside 0..%d, the range the logits kernels cover\n", n_vocab,
+                kMaxVocab);
+  return false;
+}
+
 bool read_model_file(const char* path, ModelFile& mf) {
   std::ifstream f(path, std::ios::binary);
   if (!f) {
@@ -259,6 +266,7 @@ bool read_model_file(const char* path, ModelFile& mf) {
   for (auto* p : hpf)
     if (!rd(f, *p)) return false;
   hp.ftype %= 1000;  // GGML_QNT_VERSION_FACTOR
+  if (!vocab_fits(hp.n_vocab)) return false;
 
   if (!rd(f, mf.filt_n_mel) || !rd(f, mf.filt_n_fft)) return false;
   if (mf.filt_n_mel <= 0 || mf.filt_n_fft != 1 + MWX_N_FFT / 2 ||

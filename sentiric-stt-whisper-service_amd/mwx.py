@@ -154,6 +154,21 @@ class TestGemmEncArgs(C.Structure):
                 [(n, C.POINTER(C.c_uint8)) for n in ("k8", "v8", "ks8", "vs8")])
 
 
+class TestLogitsConst(C.Structure):
+    """mwx_test_logits_const (include/mwx_test.h): the kernels' LogitsConst."""
+    __test__ = False
+    _fields_ = [(n, C.c_int) for n in ("n_vocab", "eot", "beg", "space_id", "suppress_blank",
+                                       "max_initial_tid", "nosp_id")]
+
+
+# mwx_test_logits_ctl / mwx_test_logits_out as numpy record types
+LOGITS_CTL = np.dtype([(n, "<i4") for n in ("active", "sample", "is_initial", "last_ts",
+                                            "penult_ts", "has_ts", "seek_delta", "want_probs",
+                                            "want_nosp")] + [("temperature", "<f4")])
+LOGITS_OUT = np.dtype([("id", "<i4"), ("tid", "<i4")] +
+                      [(n, "<f4") for n in ("p", "plog", "pt", "ptsum", "nosp")])
+
+
 class Prosody(C.Structure):
     """mwx_prosody = AffectiveTags (src/prosody_extractor.h:6-18)."""
     _fields_ = [(n, C.c_float) for n in ("pitch_mean", "pitch_std", "energy_mean", "energy_std",
@@ -1277,6 +1292,47 @@ class Context:
                 KS, fp(pbias), fp(te), fp(pe), ipt(tok), ipt(pos), n_tok, n_pos, fptr(y))
         self._hook_rc("mwx_test_layer_norm", rc)
         return y, x
+
+    def test_logits_process_rc(self, logits: np.ndarray, smask: np.ndarray, ctl: np.ndarray,
+                               lc: TestLogitsConst):
+        """mwx_test_logits_process: logits [R][V] f32, smask [V], ctl [R] of
+        LOGITS_CTL, lc. Returns (rc, flt, probs, logprobs [R][V], out [R] of
+        LOGITS_OUT); whatever the launch did not write is NaN (id, tid: -1)."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        smask = np.ascontiguousarray(smask, dtype=np.float32)
+        ctl = np.ascontiguousarray(ctl, dtype=LOGITS_CTL)
+        R, V = logits.shape
+        assert smask.shape == (V,) and ctl.shape == (R,)
+        flt, probs, logprobs = (np.full((R, V), np.nan, np.float32) for _ in range(3))
+        out = np.zeros(R, LOGITS_OUT)
+        out.view(np.uint32)[:] = 0xFFFFFFFF
+        fn = lib().mwx_test_logits_process
+        fpp = C.POINTER(C.c_float)
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, fpp, fpp, C.c_void_p,
+                       C.POINTER(TestLogitsConst), fpp, fpp, fpp, C.c_void_p]
+        rc = fn(self.ctx, R, V, fptr(logits), fptr(smask), ctl.ctypes.data, C.byref(lc),
+                fptr(flt), fptr(probs), fptr(logprobs), out.ctypes.data)
+        return rc, flt, probs, logprobs, out
+
+    def test_logits_process(self, logits, smask, ctl, lc):
+        """As test_logits_process_rc, raising on a non-zero return."""
+        rc, *res = self.test_logits_process_rc(logits, smask, ctl, lc)
+        self._hook_rc("mwx_test_logits_process", rc)
+        return tuple(res)
+
+    def test_logits_setup(self, params: FullParams):
+        """mwx_test_logits_setup: the engine's (LogitsConst, static mask [V]) for
+        a call with `params`."""
+        lc = TestLogitsConst()
+        smask = np.empty(self.hparam("n_vocab"), np.float32)
+        fn = lib().mwx_test_logits_setup
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(TestLogitsConst),
+                       C.POINTER(C.c_float)]
+        self._hook_rc("mwx_test_logits_setup", fn(self.ctx, C.byref(params), C.byref(lc),
+                                                  fptr(smask)))
+        return lc, smask
 
     def test_gelu_table(self) -> np.ndarray:
         """The device-built f16 GELU table as uint16 bits (index: see

@@ -41,16 +41,10 @@ import numpy as np
 import pytest
 
 import orc
+from logits_ref import N_LANG, NST  # whisper.cpp v1.8.2 non_speech_tokens
 
 torch = pytest.importorskip("torch")
 lp_mod = pytest.importorskip("transformers.generation.logits_process")
-
-# whisper.cpp v1.8.2 non_speech_tokens (whisper.cpp: whisper_process_logits)
-NST = ["\"", "#", "(", ")", "*", "+", "/", ":", ";", "<", "=", ">", "@", "[", "\\", "]", "^",
-       "_", "`", "{", "|", "}", "~", "「", "」", "『", "』", "<<", ">>", "<<<", ">>>", "--",
-       "---", "-(", "-[", "('", "(\"", "((", "))", "(((", ")))", "[[", "]]", "{{", "}}", "♪♪",
-       "♪♪♪", "♩", "♪", "♫", "♬", "♭", "♮", "♯"]
-N_LANG = 100
 
 
 class GenCfg:
