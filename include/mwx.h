@@ -698,6 +698,56 @@ bool mwx_vad_stream_in_speech(const struct mwx_vad_stream* s); /* the scan's `tr
 int mwx_vad_stream_last_kernel_ms(struct mwx_vad_context* vctx, float* stage_ms,
                                   float* frontend_ms, float* lstm_ms);
 
+/* --- transcript alignment and scoring ---------------------------
+ * Text the caller already has (a script, a corrected transcript, a subtitle
+ * line, a hypothesis of another pass) is teacher-forced through the decoder
+ * against the clip's audio: a log-probability per token and, in a context
+ * created with dtw_token_timestamps, a DTW time per token. Clip b is at most
+ * 30 s of 16 kHz audio (host or device memory, as mwx_full_batch) and
+ * n_tokens[b] text tokens, 0 .. MWX_ALIGN_MAX_TOKENS, every id below
+ * mwx_token_eot (no special, no timestamp token).
+ *
+ * The decoded sequence is the clip's sot sequence ([SOT], or [SOT, language,
+ * task] for a multilingual model), <|notimestamps|>, the tokens, EOT. Row i
+ * (0 <= i <= n) is the position that predicts token i (row n: EOT, "the text
+ * ends here"; with n = 0 the only row). From the raw logits x of that position
+ * (no suppression mask, no temperature, no timestamp rule):
+ *   plog = x[target] - logsumexp(x), p = expf(plog),
+ *   top_id = argmax x (lowest index among bit-equal values),
+ *   top_plog = x[top_id] - logsumexp(x).
+ * The logits are the bits a decode step gives for that row and position.
+ *
+ * Read from params: language ("auto" / NULL / "" runs the detection pass of
+ * mwx_full_batch), translate, audio_ctx, audio_ctx_fit (as mwx_full_batch) and
+ * the abort callback (polled before the encode: -6, and before the pass: -9).
+ * offset_ms and duration_ms must be 0 (-1, logged). Every other field is
+ * ignored: there is no previous-text prompt (initial_prompt / prompt_tokens
+ * are not used), no sampling, no fallback and no threshold.
+ *
+ * Refused before any state changes: -3 a token id outside [0, mwx_token_eot)
+ * or an unknown language; -1 (logged) n_tokens[b] > MWX_ALIGN_MAX_TOKENS,
+ * n_samples[b] > 30 * 16000, a null pointer or n_clips < 1; -5 audio_ctx >
+ * n_audio_ctx.
+ *
+ * states[b] ends with one segment: t0 = 0, t1 = the clip's length in
+ * centiseconds, the text the concatenated token strings, the tokens the given
+ * ids with p, plog, t_dtw (2 x the DTW frame, or -1 without DTW or with n = 0),
+ * tid = id, pt = ptsum = 0, t0 = t1 = -1, vlen = 0;
+ * mwx_full_lang_id_from_state returns the language used. A clip too short for
+ * mwx_full_batch to decode (under 0.1 s) ends with 0 segments and no rows. A
+ * clip's result does not depend on the other clips of the call. The decode
+ * state of a following mwx_full_batch is not affected.
+ * mwx_perf_enable class "score": the scoring kernel's launches. */
+#define MWX_ALIGN_MAX_TOKENS 224
+int mwx_align_batch(struct mwx_context* ctx, struct mwx_state* const* states,
+                    struct mwx_full_params params, const float* const* samples,
+                    const int* n_samples, const mwx_token* const* tokens, const int* n_tokens,
+                    int n_clips);
+/* Row i of the state's last mwx_align_batch, 0 <= i <= n (row n: EOT). 0, or -1
+ * out of range or without rows. Outputs are nullable. */
+int mwx_align_row(struct mwx_state* state, int i, float* plog, mwx_token* top_id,
+                  float* top_plog);
+
 #ifdef __cplusplus
 }
 #endif

@@ -423,6 +423,24 @@ int mwx_test_logits_process(struct mwx_context* ctx, int R, int V, const float* 
 int mwx_test_logits_setup(struct mwx_context* ctx, const struct mwx_full_params* params,
                           struct mwx_test_logits_const* lc, float* smask);
 
+/* --- transcript scoring on given data (tests/test_gpu_score_kernel.py) ----- */
+
+/* One score_rows launch (csrc/k_score.hip) on R rows of V raw
+ * logits [R][V] with target [R] and active [R]. Out, [R] each: plog, p, top_id,
+ * top_plog. The hook owns the device buffers; the output records start as
+ * all-ones bits (NaN; top_id = -1), so an inactive row comes back as such, and
+ * lie between two guard bands of sentinel words. Returns 0; -1 without a
+ * launch unless 1 <= R <= 4096, 1 <= V <= 53248 and every target in [0, V);
+ * -2 on a device error; -3 if the launch changed a guard band. */
+int mwx_test_score_rows(struct mwx_context* ctx, int R, int V, const float* logits,
+                        const int* target, const int* active, float* plog, float* p, int* top_id,
+                        float* top_plog);
+
+/* Rows per block of mwx_align_batch's logits buffer (default 256; 0 restores
+ * it). Returns the previous value. The result of mwx_align_batch does not
+ * depend on it. */
+int mwx_test_set_score_rows_cap(int rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -388,10 +388,18 @@ static int audio_ctx_rule(int N, int n_len_org, int seek, int audio_ctx, bool fi
   return std::min(N, std::max(floor_ctx, want));
 }
 
+// mwx_align_batch (DESIGN.md D12): run_full's mel, encode and language
+// detection, then the alignment pass over the given text instead of the window
+// loop
+struct AlignReq {
+  const mwx_token* const* tokens;
+  const int* n_tokens;
+};
+
 template <typename T>
 static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
                     const void* const* pcm, const int* n_samples, int n_clips,
-                    bool pcm16 = false) {
+                    bool pcm16 = false, const AlignReq* align = nullptr) {
   State& S = states[0]->s;
   const Hparams& hp = C.hp;
   const Vocab& vb = C.vocab;
@@ -640,6 +648,66 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
     if (cr.seek_end < cr.seek_start + delta_min) cr.finished = true;
   }
   const int n_max = P.bench_fixed_steps > 0 ? P.bench_fixed_steps : hp.n_text_ctx / 2 - 4;
+
+  // ---------------- transcript alignment (D12) ----------------
+  if (align) {
+    // the clips mwx_full_batch would decode a window of, at seek 0
+    std::vector<int> act;
+    for (int c = 0; c < n_clips; ++c) {
+      states[c]->s.align.clear();
+      if (!clips[c].finished && clips[c].seek + delta_min < clips[c].seek_end) act.push_back(c);
+    }
+    {
+      std::vector<int> which, seeks;
+      for (int c : act)
+        if (clips[c].enc_seek != 0) {
+          which.push_back(c);
+          seeks.push_back(0);
+        }
+      D.live_slots = act;
+      if (int rc = encode_clips(which, seeks, act)) return rc;
+    }
+    std::vector<typename Driver<T>::DtwClip> dc;
+    for (int c : act) {
+      typename Driver<T>::DtwClip x;
+      x.slot = c;
+      x.tokens = clips[c].prompt_init;
+      if (P.no_timestamps) x.tokens.pop_back();  // (its NOT: the first scored row)
+      x.pos0 = (int)x.tokens.size();
+      x.tokens.push_back(vb.token_not);
+      x.tokens.insert(x.tokens.end(), align->tokens[c], align->tokens[c] + align->n_tokens[c]);
+      x.tokens.push_back(vb.token_eot);
+      x.n_rows = (int)x.tokens.size() - x.pos0;
+      x.n_cols = std::max(1, std::min(D.slot_keys(c), ((int)clips[c].seek_end + 1) / 2));
+      dc.push_back(std::move(x));
+    }
+    if (!dc.empty()) {
+      if (aborted(P)) return -9;
+      std::vector<typename Driver<T>::AlignOut> out;
+      D.align_pass(dc, out, C.dtw);
+      for (size_t i = 0; i < dc.size(); ++i) {
+        const int c = dc[i].slot, n = align->n_tokens[c];
+        State& cs = states[c]->s;
+        cs.align = out[i].rows;
+        if ((int)cs.align.size() != n + 1) return -1;
+        Segment sg{0, clips[c].seek_end, "", 0.0f, {}, false};
+        for (int j = 0; j < n; ++j) {
+          mwx_token_data td;
+          memset(&td, 0, sizeof(td));
+          td.id = td.tid = align->tokens[c][j];
+          td.p = cs.align[j].p;
+          td.plog = cs.align[j].plog;
+          td.t0 = td.t1 = -1;
+          td.t_dtw = dc[i].frames.empty() ? -1 : 2 * (int64_t)dc[i].frames[j + 1];
+          sg.text += vb.id_to_token[td.id];
+          sg.tokens.push_back(td);
+        }
+        cs.result_all.push_back(std::move(sg));
+      }
+    }
+    for (int c = 0; c < n_clips; ++c) states[c]->s.lang_id = clips[c].lang_id;
+    return 0;
+  }
 
   // ---------------- window loop ----------------
   while (true) {
@@ -1652,7 +1720,7 @@ void mwx_free_state(struct mwx_state* state) {
                        &S.pf_in, &S.pf_x, &S.pf_h, &S.pf_o, &S.pf_ff, &S.pf_pqkv,
                        &S.pf_pres, &S.pf_pq, &S.perf_span,
                        &S.dtw_kself, &S.dtw_vself, &S.dtw_w, &S.dtw_cost, &S.dtw_frames,
-                       &S.dtw_meta, &S.xkeys};
+                       &S.dtw_meta, &S.xkeys, &S.sc_in, &S.sc_h, &S.sc_logits, &S.sc_out};
   for (auto* b : bufs) b->release();
   if (S.pin) (void)hipHostFree(S.pin);
   S.pin = nullptr;
@@ -1765,6 +1833,75 @@ int mwx_full_batch_pcm16(struct mwx_context* ctx, struct mwx_state* const* state
                          const int* n_samples, int n_clips) {
   return full_batch_any(ctx, states, params, reinterpret_cast<const void* const*>(samples),
                         n_samples, n_clips, true);
+}
+
+// Transcript alignment (mwx.h; DESIGN.md D12). Everything that can be refused
+// is refused before run_full touches a state.
+int mwx_align_batch(struct mwx_context* ctx, struct mwx_state* const* states,
+                    struct mwx_full_params params, const float* const* samples,
+                    const int* n_samples, const mwx_token* const* tokens, const int* n_tokens,
+                    int n_clips) {
+  if (!ctx || !states || !samples || !n_samples || !tokens || !n_tokens || n_clips < 1) {
+    MWX_LOG_ERROR("mwx_align_batch: null argument or no clips\n");
+    return -1;
+  }
+  const mwx::Hparams& hp = ctx->c.hp;
+  const mwx::Vocab& vb = ctx->c.vocab;
+  for (int c = 0; c < n_clips; ++c) {
+    if (!states[c] || (n_samples[c] > 0 && !samples[c]) || (n_tokens[c] > 0 && !tokens[c]) ||
+        n_samples[c] < 0 || n_tokens[c] < 0) {
+      MWX_LOG_ERROR("mwx_align_batch: clip %d: null state, samples or tokens\n", c);
+      return -1;
+    }
+    if (n_tokens[c] > MWX_ALIGN_MAX_TOKENS || n_tokens[c] + 5 > hp.n_text_ctx) {
+      MWX_LOG_ERROR("mwx_align_batch: clip %d: %d tokens (at most %d)\n", c, n_tokens[c],
+                    std::min(MWX_ALIGN_MAX_TOKENS, hp.n_text_ctx - 5));
+      return -1;
+    }
+    if (n_samples[c] > MWX_CHUNK_SIZE * MWX_SAMPLE_RATE) {
+      MWX_LOG_ERROR("mwx_align_batch: clip %d: %d samples (at most %d s)\n", c, n_samples[c],
+                    MWX_CHUNK_SIZE);
+      return -1;
+    }
+  }
+  if (params.offset_ms != 0 || params.duration_ms != 0) {
+    MWX_LOG_ERROR("mwx_align_batch: offset_ms and duration_ms must be 0\n");
+    return -1;
+  }
+  for (int c = 0; c < n_clips; ++c)
+    for (int j = 0; j < n_tokens[c]; ++j)
+      if (tokens[c][j] < 0 || tokens[c][j] >= vb.token_eot) return -3;
+  if (params.audio_ctx > hp.n_audio_ctx) return -5;
+  mwx_full_params P = mwx_full_default_params(MWX_SAMPLING_GREEDY);
+  P.language = params.language;
+  P.translate = params.translate;
+  P.audio_ctx = params.audio_ctx;
+  P.audio_ctx_fit = params.audio_ctx_fit;
+  P.abort_callback = params.abort_callback;
+  P.abort_callback_user_data = params.abort_callback_user_data;
+  const bool detect =
+      P.language == nullptr || strlen(P.language) == 0 || strcmp(P.language, "auto") == 0;
+  if (!detect && vb.is_multilingual() && mwx::lang_id(P.language) < 0) return -3;
+  const mwx::AlignReq req{tokens, n_tokens};
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    const void* const* pcm = reinterpret_cast<const void* const*>(samples);
+    if (ctx->c.wtype == mwx::GGML_BF16)
+      return mwx::run_full<__bf16>(ctx->c, states, P, pcm, n_samples, n_clips, false, &req);
+    return mwx::run_full<_Float16>(ctx->c, states, P, pcm, n_samples, n_clips, false, &req);
+  } catch (...) {
+    return -1;
+  }
+}
+
+int mwx_align_row(struct mwx_state* state, int i, float* plog, mwx_token* top_id,
+                  float* top_plog) {
+  if (!state || i < 0 || i >= (int)state->s.align.size()) return -1;
+  const mwx::ScoreOut& r = state->s.align[i];
+  if (plog) *plog = r.plog;
+  if (top_id) *top_id = r.top_id;
+  if (top_plog) *top_plog = r.top_plog;
+  return 0;
 }
 
 // Trimmed audio (vad.cpp, mwx_vad_trim_batch) through the batched path: the
@@ -3703,4 +3840,48 @@ extern "C" int mwx_test_dtw_align(struct mwx_context* ctx, struct mwx_state* sta
   } catch (...) {
     return -2;
   }
+}
+
+// ---------------------------------------------------------------------------
+// Transcript scoring on given data (k_score.hip), and the alignment pass's
+// logits block size
+// ---------------------------------------------------------------------------
+extern "C" int mwx_test_score_rows(struct mwx_context* ctx, int R, int V, const float* logits,
+                                   const int* target, const int* active, float* plog, float* p,
+                                   int* top_id, float* top_plog) {
+  if (!ctx || !logits || !target || !active || !plog || !p || !top_id || !top_plog) return -1;
+  if (R < 1 || R > 4096 || V < 1 || V > mwx::SCORE_MAX_VOCAB) return -1;
+  for (int r = 0; r < R; ++r)
+    if (target[r] < 0 || target[r] >= V) return -1;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    const size_t rv = (size_t)R * V * 4;
+    DevScratch m;
+    float* dl = (float*)m.get(rv);
+    int* dt = (int*)m.get((size_t)R * 4);
+    int* da = (int*)m.get((size_t)R * 4);
+    HIPC(hipMemcpy(dl, logits, rv, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dt, target, (size_t)R * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(da, active, (size_t)R * 4, hipMemcpyHostToDevice));
+    GuardedBuf go;
+    mwx::ScoreOut* dout = (mwx::ScoreOut*)go.make(m, (size_t)R * sizeof(mwx::ScoreOut), nullptr);
+    if (!mwx::score_rows(dl, dt, da, R, V, dout, nullptr)) return -1;
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    std::vector<mwx::ScoreOut> ho(R);
+    if (!go.take(ho.data())) return -3;
+    for (int r = 0; r < R; ++r) {
+      plog[r] = ho[r].plog;
+      p[r] = ho[r].p;
+      top_id[r] = ho[r].top_id;
+      top_plog[r] = ho[r].top_plog;
+    }
+    return 0;
+  } catch (...) {
+    return -2;
+  }
+}
+
+extern "C" int mwx_test_set_score_rows_cap(int rows) {
+  return mwx::score_rows_cap_var().exchange(rows > 0 ? rows : mwx::kScoreRowsCap);
 }

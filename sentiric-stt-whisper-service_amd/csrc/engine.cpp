@@ -290,6 +290,15 @@ struct State {
   // on the host (mwx_test_dtw_last reads them; cleared by each mwx_full* call)
   DBuf dtw_kself, dtw_vself, dtw_w, dtw_cost, dtw_frames, dtw_meta;
   int dtw_rows = 0;
+  // transcript alignment: the scored rows' [target|active]
+  // words of one prefill chunk, a block's final-LayerNorm output (decode-GEMM A
+  // tiles) and its logits [score_rows_cap][n_vocab] (never S.logits), and the
+  // pass's score records; sc_hin: the host side of sc_in for every chunk (read
+  // by stream-ordered uploads until the pass synchronizes). align: the rows of
+  // the state's last mwx_align_batch (mwx_align_row)
+  DBuf sc_in, sc_h, sc_logits, sc_out;
+  std::vector<int> sc_hin;
+  std::vector<ScoreOut> align;
   bool dtw_keep = false;
   struct DtwDump {
     int N = 0, T = 0, A = 0, n_keys = 0;
@@ -331,6 +340,15 @@ struct State {
   size_t span_gused = 0, span_eused = 0;
   double span_tick_ms = 0.0;  // ms per s_memrealtime tick
 };
+
+// Rows per block of the alignment pass's logits buffer:
+// mwx_test_set_score_rows_cap switches it, 0 restores the default
+constexpr int kScoreRowsCap = 256;
+static std::atomic<int>& score_rows_cap_var() {
+  static std::atomic<int> v{kScoreRowsCap};
+  return v;
+}
+static int score_rows_cap() { return std::max(1, score_rows_cap_var().load()); }
 
 static void harvest_events(std::vector<hipEvent_t>& ev, const std::vector<int>& tag, size_t used,
                            State& S) {
@@ -1516,9 +1534,22 @@ struct Driver {
   // alignment launches, not counted as prompt prefill
   struct DtwRows {
     int rows, pos0, rows_cap;
-    float* out;
+    float* out;  // (nullptr: no alignment launches, the pass only scores)
   };
-  void prefill(const std::vector<PrefillRow>& prs, const DtwRows* dtw = nullptr) {
+  // score != nullptr (align_pass): after each chunk's layers,
+  // the virtual rows at positions pos0 .. n - 2 of every prompt (the last
+  // position, EOT, is never scored) get the final LayerNorm and the logits GEMM
+  // exactly as step_tail forms them, in blocks of at most score_rows_cap rows
+  // through S.sc_logits, and score_rows against the next token of the prompt.
+  // where[i][p - pos0]: the index in out of prompt i's position p.
+  struct ScoreRows {
+    int pos0 = 0;
+    ScoreOut* out = nullptr;
+    size_t n_out = 0;
+    std::vector<std::vector<int>> where;
+  };
+  void prefill(const std::vector<PrefillRow>& prs, const DtwRows* dtw = nullptr,
+               ScoreRows* score = nullptr) {
     static const int vcap = std::max(64, getenv("MWX_PREFILL_ROWS")
                                              ? atoi(getenv("MWX_PREFILL_ROWS")) : 2048);
     int nmax = 0, nrows = 0;
@@ -1571,6 +1602,21 @@ struct Driver {
     for (int p0 = 0; p0 < nmax; p0 += span) ++chunks;
     S.pf_hin.clear();
     S.pf_hin.reserve(chunks * mcap * 5);
+    const int sc_cap = score_rows_cap();
+    int* sc_din = nullptr;
+    T* sc_h = nullptr;
+    float* sc_logits = nullptr;
+    size_t chunk_i = 0;
+    if (score) {
+      sc_din = (int*)S.sc_in.get(mcap * 2 * 4);
+      sc_h = (T*)S.sc_h.get((size_t)(sc_cap + 63) / 64 * 64 * d * sizeof(T), true);
+      sc_logits = (float*)S.sc_logits.get((size_t)sc_cap * V * 4);
+      score->n_out = chunks * mcap;
+      score->out = (ScoreOut*)S.sc_out.get(score->n_out * sizeof(ScoreOut));
+      score->where.assign(prs.size(), {});
+      S.sc_hin.clear();
+      S.sc_hin.reserve(chunks * mcap * 2);
+    }
     // MWX_PREFILL_TIME=1: device time of the pass (events) and host time of
     // the call on stderr (diagnostic)
     static const bool timing = getenv("MWX_PREFILL_TIME") && atoi(getenv("MWX_PREFILL_TIME")) != 0;
@@ -1582,13 +1628,20 @@ struct Driver {
       HIPC(hipEventRecord(ev0, st));
     }
     for (int p0 = 0; p0 < nmax; p0 += span) {
-      std::vector<int> tok, pos, act, xidx, crow;
-      for (const auto& r : prs) {
+      std::vector<int> tok, pos, act, xidx, crow, tgt, sact;
+      for (size_t ri = 0; ri < prs.size(); ++ri) {
+        const PrefillRow& r = prs[ri];
         const int len = std::min(r.n, p0 + span) - p0;
         if (len <= 0) continue;
         const int padded = (len + q - 1) / q * q;
         for (int j = 0; j < padded; ++j) {
           const bool a = j < len;
+          if (score) {
+            const bool sc = a && p0 + j >= score->pos0 && p0 + j + 1 < r.n;
+            if (sc) score->where[ri].push_back((int)(chunk_i * mcap + tok.size()));
+            tgt.push_back(sc ? r.tokens[p0 + j + 1] : 0);
+            sact.push_back(sc ? 1 : 0);
+          }
           tok.push_back(a ? r.tokens[p0 + j] : 0);
           pos.push_back(a ? p0 + j : 0);
           act.push_back(a ? 1 : 0);
@@ -1614,7 +1667,38 @@ struct Driver {
       rw.crow = din + 4 * M;
       int ks_prev = 0;
       const float* bias_prev = nullptr;
-      run_layers(rw, st, ks_prev, bias_prev);
+      float* xd = rw.xd;
+      run_layers(rw, st, ks_prev, bias_prev, &xd);
+      if (score) {
+        const size_t s0 = S.sc_hin.size();
+        S.sc_hin.insert(S.sc_hin.end(), tgt.begin(), tgt.end());
+        S.sc_hin.insert(S.sc_hin.end(), sact.begin(), sact.end());
+        HIPC(hipMemcpyAsync(sc_din, S.sc_hin.data() + s0, (size_t)2 * M * 4, hipMemcpyHostToDevice,
+                            st));
+        for (int r0 = 0; r0 < M; r0 += sc_cap) {
+          const int nb = std::min(sc_cap, M - r0);
+          bool any = false;
+          for (int j = 0; j < nb; ++j) any |= sact[r0 + j] != 0;
+          if (!any) continue;
+          const int* bact = sc_din + M + r0;
+          // (step_tail's final LayerNorm and tied-embedding logits of the
+          // block's scored rows: the slabs keep the chunk's stride)
+          layer_norm_dec_rows<T>(xd + (size_t)r0 * d, C.dec_ln_w, C.dec_ln_b, sc_h, nb, d, bact, st,
+                                 rw.Pres + (size_t)r0 * d, ks_prev, (long)M * d, bias_prev);
+          EpiParams e;
+          e.c32 = sc_logits;
+          e.ldc = V;
+          e.mt = nb <= 64 ? std::max(1, (nb + 15) / 16) : 2;
+          { PerfScope ps(S, "logits_gemm", st);
+            if (!gemm_decode<T>(EPI_F32, sc_h, Dw(C.tok_p), nb, V, d, e, st))
+              throw std::runtime_error("mwx: unsupported logits GEMM shape"); }
+          PerfScope ps(S, "score", st);
+          if (!score_rows(sc_logits, sc_din + r0, bact, nb, V,
+                          score->out + chunk_i * mcap + r0, st))
+            throw std::runtime_error("mwx: unsupported score shape");
+        }
+      }
+      ++chunk_i;
     }
     if (timing) {
       HIPC(hipEventRecord(ev1, st));
@@ -1716,6 +1800,90 @@ struct Driver {
       kept = true;
     }
     if (kept) HIPC(hipStreamSynchronize(st));
+  }
+
+  // Transcript alignment: dtw_pass's teacher-forced prefill
+  // over the DTW self cache, with the score tail on the rows at positions pos0
+  // .. pos0 + n (n = n_rows - 2 text tokens), and, when `times` is set (a
+  // context with alignment heads, clips with n > 0), the alignment, cost and
+  // path launches of dtw_pass; scores and frames come back in one synchronize.
+  // The decode rows' caches, position maps and run-ahead state are not touched.
+  struct AlignOut {
+    std::vector<ScoreOut> rows;  // [n + 1]
+  };
+  void align_pass(std::vector<DtwClip>& dc, std::vector<AlignOut>& out, bool times) {
+    const int nB = (int)dc.size();
+    if (nB == 0) return;
+    const int A = (int)C.dtw_heads.size(), n_keys = hp.n_audio_ctx;
+    int ncap = 0, tmax = 0;
+    for (const auto& c : dc) {
+      ncap = std::max(ncap, c.n_rows);
+      tmax = std::max(tmax, c.n_cols);
+    }
+    const size_t per = (size_t)L_dec * H * Tctx * 64 * 2;
+    if (S.dtw_rows < nB) {
+      S.dtw_kself.release();
+      S.dtw_vself.release();
+      S.dtw_kself.get(per * nB);
+      S.dtw_vself.get(per * nB);
+      S.dtw_rows = nB;
+    }
+    const size_t wclip = (size_t)A * ncap * n_keys;
+    const long cstride = (long)ncap * tmax;
+    float* w = nullptr;
+    float* cost = nullptr;
+    int* frames = nullptr;
+    int* meta = nullptr;
+    // the clips that get times: those with text (n_rows > 2, as run_full)
+    std::vector<int> tl;
+    for (int i = 0; i < nB && times; ++i)
+      if (dc[i].n_rows > 2) tl.push_back(i);
+    times = !tl.empty();
+    const int nT = (int)tl.size();
+    std::vector<int> hm(3 * std::max(1, nT));
+    if (times) {
+      w = (float*)S.dtw_w.get((size_t)S.cross_cap * wclip * 4);
+      cost = (float*)S.dtw_cost.get((size_t)nT * cstride * 4);
+      frames = (int*)S.dtw_frames.get((size_t)nT * ncap * 4);
+      meta = (int*)S.dtw_meta.get((size_t)3 * nT * 4);
+    }
+    std::vector<PrefillRow> prs;
+    for (int i = 0; i < nB; ++i)
+      prs.push_back({i, dc[i].slot, dc[i].tokens.data(), (int)dc[i].tokens.size()});
+    for (int k = 0; k < nT; ++k) {
+      hm[k] = dc[tl[k]].slot;
+      hm[nT + k] = dc[tl[k]].n_rows;
+      hm[2 * nT + k] = dc[tl[k]].n_cols;
+    }
+    if (times) HIPC(hipMemcpyAsync(meta, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, st));
+    const DtwRows dr{S.dtw_rows, dc[0].pos0, ncap, w};  // (w = nullptr: no alignment launches)
+    ScoreRows sr;
+    sr.pos0 = dc[0].pos0;
+    prefill(prs, &dr, &sr);
+    std::vector<int> hf;
+    if (times) {
+      { PerfScope ps(S, "dtw_cost", st);
+        if (!dtw_cost(w, meta, meta + nT, meta + 2 * nT, nT, A, ncap, n_keys, tmax, cstride, cost,
+                      st))
+          throw std::runtime_error("mwx: unsupported DTW cost shape"); }
+      { PerfScope ps(S, "dtw_path", st);
+        if (!dtw_path(cost, meta + nT, meta + 2 * nT, nT, ncap, tmax, cstride, ncap, frames, 0,
+                      nullptr, nullptr, st))
+          throw std::runtime_error("mwx: unsupported DTW path shape"); }
+      hf.resize((size_t)nT * ncap);
+      HIPC(hipMemcpyAsync(hf.data(), frames, hf.size() * 4, hipMemcpyDeviceToHost, st));
+    }
+    std::vector<ScoreOut> hs(sr.n_out);
+    HIPC(hipMemcpyAsync(hs.data(), sr.out, hs.size() * sizeof(ScoreOut), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    out.assign(nB, {});
+    for (int i = 0; i < nB; ++i) {
+      dc[i].frames.clear();
+      for (int at : sr.where[i]) out[i].rows.push_back(hs[at]);
+    }
+    for (int k = 0; k < nT; ++k)
+      dc[tl[k]].frames.assign(hf.begin() + (size_t)k * ncap,
+                              hf.begin() + (size_t)k * ncap + dc[tl[k]].n_rows);
   }
 
   // the decode-step rows (all R) and their buffers

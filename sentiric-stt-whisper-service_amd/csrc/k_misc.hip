@@ -206,6 +206,18 @@ void layer_norm_dec(float* x, const float* w, const float* b, T* y, int M, int N
                     const float* pbias, const EmbedIn<T>& emb) {
   ln_dec_kernel<T><<<M, 256, 0, st>>>(x, w, b, y, N, active, P, KS, (long)M * N, pbias, emb);
 }
+template <typename T>
+void layer_norm_dec_rows(float* x, const float* w, const float* b, T* y, int M, int N,
+                         const int* active, hipStream_t st, const float* P, int KS, long pstride,
+                         const float* pbias) {
+  ln_dec_kernel<T><<<M, 256, 0, st>>>(x, w, b, y, N, active, P, KS, pstride, pbias, EmbedIn<T>());
+}
+template void layer_norm_dec_rows<_Float16>(float*, const float*, const float*, _Float16*, int, int,
+                                            const int*, hipStream_t, const float*, int, long,
+                                            const float*);
+template void layer_norm_dec_rows<__bf16>(float*, const float*, const float*, __bf16*, int, int,
+                                          const int*, hipStream_t, const float*, int, long,
+                                          const float*);
 
 template void layer_norm<_Float16>(const float*, const float*, const float*, _Float16*, int, int,
                                    const int*, hipStream_t, const float*, int, const float*);

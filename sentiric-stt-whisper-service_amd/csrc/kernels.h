@@ -212,6 +212,14 @@ template <typename T>
 void layer_norm_dec(float* x, const float* w, const float* b, T* y, int M, int N,
                     const int* active, hipStream_t st, const float* P, int KS,
                     const float* pbias, const EmbedIn<T>& emb = EmbedIn<T>());
+// The same kernel over M consecutive rows of a larger launch's buffers: x, P
+// and active point at the first of them, pstride is the slabs' stride in the
+// producing launch (rows x N), y receives the rows as tiles 0 .. M - 1. A row's
+// arithmetic is layer_norm_dec's.
+template <typename T>
+void layer_norm_dec_rows(float* x, const float* w, const float* b, T* y, int M, int N,
+                         const int* active, hipStream_t st, const float* P, int KS, long pstride,
+                         const float* pbias);
 
 
 // encoder self-attention: q,k [B][H][L][64], vt [B][H][64][L] f16 -> o [B*L][H*64] (T)
@@ -452,6 +460,21 @@ struct LPScratch {
 void logits_process(float* logits, const float* static_mask, const RowCtl* ctl, TokOut* out,
                     float* probs, float* logprobs, const LogitsConst& C, int R, LPScratch ws,
                     hipStream_t st, bool pick = true);
+
+// Transcript scoring (k_score.hip): for every row r with
+// active[r] (nullptr: all), from its raw logits x = logits + r V:
+// plog = x[target[r]] - logsumexp(x), p = expf(plog), top_id = the lowest-index
+// argmax of x, top_plog = x[top_id] - logsumexp(x). One workgroup per row and a
+// fixed combine order: a row's bits do not depend on R or on the other rows.
+// An inactive row writes nothing; target[r] of an active row is in [0, V).
+// false (no launch) for R < 1, V < 1 or V > SCORE_MAX_VOCAB.
+constexpr int SCORE_MAX_VOCAB = LP_G * LP_CHUNK;
+struct ScoreOut {
+  float plog, p, top_plog;
+  int top_id;
+};
+bool score_rows(const float* logits, const int* target, const int* active, int R, int V,
+                ScoreOut* out, hipStream_t st);
 
 // std::discrete_distribution draws from the probs rows (k_misc.hip):
 // out[row][d] for d < ndraw[row] (<= KD <= 16), u[row][d] =

@@ -62,6 +62,30 @@ std::string to_json(const std::vector<TranscriptionResult>& rs) {
   return o + "]";
 }
 
+// AlignmentResult: floats as their f32 bit patterns (a log-probability may be
+// -inf, which JSON cannot carry)
+unsigned f32_bits(float v) {
+  unsigned u;
+  std::memcpy(&u, &v, 4);
+  return u;
+}
+std::string to_json(const AlignmentResult& r) {
+  char buf[256];
+  std::snprintf(buf, sizeof buf, "{\"ok\":%d,\"avg_logprob\":%u,\"eot_logprob\":%u,\"n_agree\":%d,",
+                (int)r.ok, f32_bits(r.avg_logprob), f32_bits(r.eot_logprob), r.n_agree);
+  std::string o = buf;
+  o += "\"text\":\"" + hex(r.text) + "\",\"language\":\"" + hex(r.language) + "\",\"tokens\":[";
+  for (size_t j = 0; j < r.tokens.size(); ++j) {
+    const AlignedToken& t = r.tokens[j];
+    std::snprintf(buf, sizeof buf, "%s{\"id\":%d,\"p\":%u,\"plog\":%u,\"t\":%lld,\"top_id\":%d,"
+                  "\"top_plog\":%u,\"text\":\"", j ? "," : "", t.id, f32_bits(t.p), f32_bits(t.plog),
+                  (long long)t.t, t.top_id, f32_bits(t.top_plog));
+    o += buf;
+    o += hex(t.text) + "\",\"top_text\":\"" + hex(t.top_text) + "\"}";
+  }
+  return o + "]}";
+}
+
 int emit(const std::string& s, char* out, int cap) {
   if ((int)s.size() + 1 > cap) return -(int)(s.size() + 1);
   std::memcpy(out, s.c_str(), s.size() + 1);
@@ -282,6 +306,54 @@ int mwx_stt_transcribe_batch_f32(void* eng, const float* const* pcm, const int* 
     j += "]";
     const int r = emit(j, out, cap);
     return r < -1 ? r - 2 : r;
+  } catch (const EngineBusyException&) {
+    return -2;
+  } catch (...) {
+    return -1;
+  }
+}
+
+// SttEngine::align_pcm16 / align: one AlignmentResult as JSON (strings
+// hex-encoded, floats as f32 bit patterns). Return codes as
+// mwx_stt_transcribe_pcm16.
+int mwx_stt_align_pcm16(void* eng, const int16_t* pcm, int n, int sample_rate, const char* text,
+                        const char* language, int translate, char* out, int cap) {
+  RequestOptions o;
+  o.language = language ? language : "";
+  o.translate = translate != 0;
+  try {
+    const AlignmentResult r = static_cast<SttEngine*>(eng)->align_pcm16(
+        std::vector<int16_t>(pcm, pcm + n), sample_rate, text ? text : "", o);
+    const int rc = emit(to_json(r), out, cap);
+    return rc < -1 ? rc - 2 : rc;
+  } catch (const EngineBusyException&) {
+    return -2;
+  } catch (...) {
+    return -1;
+  }
+}
+
+// SttEngine::align_batch over n_clips f32 clips at 16 kHz and their texts: a
+// JSON list with one AlignmentResult per clip.
+int mwx_stt_align_batch_f32(void* eng, const float* const* pcm, const int* n,
+                            const char* const* texts, int n_clips, const char* language,
+                            int translate, char* out, int cap) {
+  RequestOptions o;
+  o.language = language ? language : "";
+  o.translate = translate != 0;
+  try {
+    std::vector<std::vector<float>> clips;
+    std::vector<std::string> tx;
+    for (int b = 0; b < n_clips; ++b) {
+      clips.emplace_back(pcm[b], pcm[b] + n[b]);
+      tx.emplace_back(texts[b] ? texts[b] : "");
+    }
+    const auto rs = static_cast<SttEngine*>(eng)->align_batch(clips, tx, o);
+    std::string j = "[";
+    for (size_t b = 0; b < rs.size(); ++b) j += (b ? "," : "") + to_json(rs[b]);
+    j += "]";
+    const int rc = emit(j, out, cap);
+    return rc < -1 ? rc - 2 : rc;
   } catch (const EngineBusyException&) {
     return -2;
   } catch (...) {

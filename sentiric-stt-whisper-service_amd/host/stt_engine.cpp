@@ -42,6 +42,13 @@
 #pragma weak mwx_vad_stream_max_prob
 #pragma weak mwx_vad_stream_n_segments
 #pragma weak mwx_vad_stream_segment
+// ... and the alignment calls (with the three lookups only align() uses):
+// without them align() returns ok = false
+#pragma weak mwx_align_batch
+#pragma weak mwx_align_row
+#pragma weak mwx_tokenize
+#pragma weak mwx_full_lang_id_from_state
+#pragma weak mwx_lang_str
 
 namespace mwx_host {
 
@@ -207,6 +214,8 @@ SttEngine::SttEngine(const Settings& settings) : settings_(settings) {
   aux_state_ = mwx_init_state(ctx_);
   if (!aux_state_) throw std::runtime_error("Whisper state initialization failed");
   all_states_.push_back(aux_state_);
+  align_bound_ = mwx_align_batch && mwx_align_row && mwx_tokenize && mwx_full_lang_id_from_state &&
+                 mwx_lang_str;
   // src/stt_engine.cpp:44-55: a VAD model that does not load is logged and the
   // engine carries on without the gate
   if (settings_.enable_vad) {
@@ -737,6 +746,153 @@ std::vector<TranscriptionResult> SttEngine::transcribe_impl(const std::vector<fl
   }
   return collect(state, lang, pcm.data(), pcm_size, options.prosody_opts,
                  out_metrics ? &out_metrics->token_count : nullptr);
+}
+
+// ---- transcript alignment ---------------------------------------------------
+std::vector<AlignmentResult> SttEngine::align_run(mwx_state* const* states,
+                                                  const std::vector<const std::vector<float>*>& clips,
+                                                  const std::vector<std::string>& texts,
+                                                  const RequestOptions& options) {
+  const size_t B = clips.size();
+  std::vector<AlignmentResult> out(B);
+  std::vector<std::vector<mwx_token>> toks(B);
+  for (size_t b = 0; b < B; ++b) {
+    // trimmed, one leading space (the form Whisper's text tokens take after a
+    // special token)
+    const size_t a = texts[b].find_first_not_of(" \t\r\n");
+    const size_t z = texts[b].find_last_not_of(" \t\r\n");
+    const std::string t = a == std::string::npos ? "" : " " + texts[b].substr(a, z - a + 1);
+    if (!t.empty()) {
+      toks[b].resize(MWX_ALIGN_MAX_TOKENS);
+      const int n = mwx_tokenize(ctx_, t.c_str(), toks[b].data(), MWX_ALIGN_MAX_TOKENS);
+      if (n < 0) {
+        std::fprintf(stderr, "SttEngine: align: %d tokens, at most %d\n", -n, MWX_ALIGN_MAX_TOKENS);
+        return out;
+      }
+      toks[b].resize(static_cast<size_t>(n));
+    }
+    if (clips[b]->size() > static_cast<size_t>(MWX_CHUNK_SIZE) * MWX_SAMPLE_RATE) {
+      std::fprintf(stderr, "SttEngine: align: %zu samples, at most %d s\n", clips[b]->size(),
+                   MWX_CHUNK_SIZE);
+      return out;
+    }
+  }
+  std::string lang;
+  std::function<bool()> abort_fn = options.should_abort;
+  const mwx_full_params p = make_params(options, lang, abort_fn);
+  std::vector<const float*> ptrs;
+  std::vector<int> lens, ntok;
+  std::vector<const mwx_token*> tptr;
+  for (size_t b = 0; b < B; ++b) {
+    ptrs.push_back(clips[b]->data());
+    lens.push_back(static_cast<int>(clips[b]->size()));
+    tptr.push_back(toks[b].data());
+    ntok.push_back(static_cast<int>(toks[b].size()));
+  }
+  const int ret = mwx_align_batch(ctx_, states, p, ptrs.data(), lens.data(), tptr.data(),
+                                  ntok.data(), static_cast<int>(B));
+  if (ret != 0) {
+    std::fprintf(stderr, "SttEngine: align failed: %d\n", ret);
+    return out;
+  }
+  for (size_t b = 0; b < B; ++b) {
+    AlignmentResult& r = out[b];
+    const int n = ntok[b];
+    if (mwx_full_n_segments_from_state(states[b]) != 1 ||
+        mwx_full_n_tokens_from_state(states[b], 0) != n) {
+      std::fprintf(stderr, "SttEngine: align: clip %zu too short to align\n", b);
+      continue;
+    }
+    const char* tc = mwx_full_get_segment_text_from_state(states[b], 0);
+    r.text = tc ? tc : "";
+    const char* ls = mwx_lang_str(mwx_full_lang_id_from_state(states[b]));
+    r.language = ls ? ls : "";
+    double sum = 0.0;
+    bool rows = true;
+    for (int j = 0; j < n && rows; ++j) {
+      const mwx_token_data d = mwx_full_get_token_data_from_state(states[b], 0, j);
+      AlignedToken t;
+      const char* ts = mwx_token_to_str(ctx_, d.id);
+      t.text = ts ? ts : "";
+      t.id = d.id;
+      t.p = d.p;
+      t.plog = d.plog;
+      t.t = d.t_dtw;
+      mwx_token top = 0;
+      rows = mwx_align_row(states[b], j, nullptr, &top, &t.top_plog) == 0;
+      t.top_id = top;
+      const char* tt = mwx_token_to_str(ctx_, top);
+      t.top_text = tt ? tt : "";
+      r.n_agree += t.top_id == t.id;
+      sum += d.plog;
+      r.tokens.push_back(std::move(t));
+    }
+    rows = rows && mwx_align_row(states[b], n, &r.eot_logprob, nullptr, nullptr) == 0;
+    if (!rows) {
+      std::fprintf(stderr, "SttEngine: align: clip %zu has no score rows\n", b);
+      r = AlignmentResult();
+      continue;
+    }
+    r.avg_logprob = n > 0 ? static_cast<float>(sum / n) : 0.0f;
+    r.ok = true;
+  }
+  return out;
+}
+
+std::vector<AlignmentResult> SttEngine::align_batch(const std::vector<std::vector<float>>& clips16k,
+                                                    const std::vector<std::string>& texts,
+                                                    const RequestOptions& options) {
+  std::vector<AlignmentResult> out(clips16k.size());
+  if (!ctx_ || clips16k.empty()) return out;
+  if (!align_bound_) {
+    std::fprintf(stderr, "SttEngine: align: the library has no alignment calls\n");
+    return out;
+  }
+  if (clips16k.size() != texts.size()) {
+    std::fprintf(stderr, "SttEngine: align: %zu clips, %zu texts\n", clips16k.size(), texts.size());
+    return out;
+  }
+  std::lock_guard<std::mutex> batch_lock(batch_mutex_);
+  while (batch_states_.size() < clips16k.size()) {
+    mwx_state* st = mwx_init_state(ctx_);
+    if (!st) return out;
+    batch_states_.push_back(st);
+    all_states_.push_back(st);
+  }
+  std::vector<const std::vector<float>*> clips;
+  for (const auto& c : clips16k) clips.push_back(&c);
+  return align_run(batch_states_.data(), clips, texts, options);
+}
+
+AlignmentResult SttEngine::align(const std::vector<float>& pcmf32, int sample_rate,
+                                 const std::string& text, const RequestOptions& options) {
+  if (!ctx_) return {};
+  if (!align_bound_) {
+    std::fprintf(stderr, "SttEngine: align: the library has no alignment calls\n");
+    return {};
+  }
+  if (options.should_abort && options.should_abort()) return {};
+  std::vector<float> resampled;
+  if (sample_rate != 16000)
+    resampled = resample_audio(pcmf32.data(), pcmf32.size(), sample_rate, 16000);
+  const std::vector<float>& pcm = resampled.empty() ? pcmf32 : resampled;
+  // (with the request batcher on, the pool's states belong to the batchers:
+  // the states kept for batch calls serve instead)
+  if (settings_.max_batch > 1) {
+    std::vector<AlignmentResult> r = align_batch({pcm}, {text}, options);
+    return r.empty() ? AlignmentResult() : std::move(r[0]);
+  }
+  StateGuard guard(*this);
+  mwx_state* state = guard.get();
+  std::vector<AlignmentResult> r = align_run(&state, {&pcm}, {text}, options);
+  return r.empty() ? AlignmentResult() : std::move(r[0]);
+}
+
+AlignmentResult SttEngine::align_pcm16(const std::vector<int16_t>& pcm16, int sample_rate,
+                                       const std::string& text, const RequestOptions& options) {
+  std::vector<float> f(pcm16.size());
+  for (size_t i = 0; i < pcm16.size(); ++i) f[i] = static_cast<float>(pcm16[i]) / 32768.0f;
+  return align(f, sample_rate, text, options);
 }
 
 std::vector<float> SttEngine::resample_audio(const float* input, size_t input_size, int src_rate,

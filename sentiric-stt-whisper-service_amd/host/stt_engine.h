@@ -225,6 +225,29 @@ struct TranscriptionResult {
   std::string speaker_id;
 };
 
+// Transcript alignment (SttEngine::align; mwx.h mwx_align_batch, rule D12):
+// the caller's text, teacher-forced against the audio. One entry per text
+// token: its log-probability given the audio and the text before it, its DTW
+// time (10 ms units; -1 unless Settings::dtw_token_timestamps) and the model's
+// own first choice at that position.
+struct AlignedToken {
+  std::string text;
+  int id;
+  float p, plog;
+  int64_t t;  // t_dtw or -1
+  int top_id;
+  std::string top_text;
+  float top_plog;
+};
+struct AlignmentResult {
+  bool ok = false;
+  std::string text, language;
+  float avg_logprob = 0;  // mean plog of the tokens (0 without tokens)
+  float eot_logprob = 0;  // log-probability that the text ends after its last token
+  int n_agree = 0;        // tokens with top_id == id
+  std::vector<AlignedToken> tokens;
+};
+
 class EngineBusyException : public std::runtime_error {
  public:
   explicit EngineBusyException(const std::string& msg) : std::runtime_error(msg) {}
@@ -284,6 +307,27 @@ class SttEngine {
   // batch call at a time).
   std::vector<std::vector<TranscriptionResult>> transcribe_batch(
       const std::vector<std::vector<float>>& clips, const RequestOptions& options);
+
+  // Transcript alignment (no reference counterpart): scores and DTW times of
+  // `text` against at most 30 s of audio. The audio is resampled as
+  // transcribe() resamples it; the text is trimmed, prefixed with one space and
+  // tokenised (at most 224 tokens). No VAD gate, no minimum-duration gate, no
+  // post-filter, no prompt (RequestOptions::prompt is not used); language as in
+  // transcribe() ("auto" detects), the result's language is the one used. Any
+  // failure (too many tokens, audio over 30 s, an engine error, a library
+  // without the alignment calls) is logged and gives ok = false; the state
+  // pool's timeout throws EngineBusyException as transcribe() does. The
+  // request batcher is not involved.
+  AlignmentResult align(const std::vector<float>& pcm, int sample_rate, const std::string& text,
+                        const RequestOptions& options);
+  AlignmentResult align_pcm16(const std::vector<int16_t>& pcm16, int sample_rate,
+                              const std::string& text, const RequestOptions& options);
+  // B independent 16 kHz clips and their texts in one GPU pass, on the states
+  // kept for batch calls; clips.size() != texts.size() fails every entry.
+  std::vector<AlignmentResult> align_batch(const std::vector<std::vector<float>>& clips16k,
+                                           const std::vector<std::string>& texts,
+                                           const RequestOptions& options);
+  bool align_available() const { return align_bound_; }
 
   // SttEngine::resample_audio (src/stt_engine.cpp:87-106) on the GPU
   // (mwx_resample): empty when src_rate == target_rate, the input is empty or
@@ -370,6 +414,12 @@ class SttEngine {
                                               int n_clips);
   bool trim_active_ = false;  // vad_trim, a VAD context and a library that has the calls
   bool chunk_bound_ = false;  // the library has the chunked calls
+  bool align_bound_ = false;  // the library has the alignment calls
+  // mwx_align_batch on `states` and the results of its clips
+  std::vector<AlignmentResult> align_run(mwx_state* const* states,
+                                         const std::vector<const std::vector<float>*>& clips,
+                                         const std::vector<std::string>& texts,
+                                         const RequestOptions& options);
   bool stream_gate_active_ = false;      // stream_vad, the gate path and the stream calls
   bool stream_endpoint_active_ = false;  // stream_endpoint_silence_ms, a VAD context, the calls
   std::atomic<long> vad_gate_runs_{0};

@@ -512,6 +512,57 @@ def set_ra_mismatch(step: Optional[int]) -> int:
     return lib().mwx_test_set_ra_mismatch(-2 if step is None else int(step))
 
 
+def set_score_rows_cap(rows: int = 0) -> int:
+    """mwx_test_set_score_rows_cap: rows per block of align_batch's logits
+    buffer (0: the default, 256). Returns the previous value."""
+    fn = lib().mwx_test_set_score_rows_cap
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int]
+    return fn(int(rows))
+
+
+def stt_lib() -> C.CDLL:
+    """libmwx_stt.so (the host SttEngine's C glue) with the alignment calls typed."""
+    L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmwx_stt.so"))
+    L.mwx_stt_new.restype = C.c_void_p
+    L.mwx_stt_new.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p,
+                              C.c_int, C.c_int]
+    L.mwx_stt_free.argtypes = [C.c_void_p]
+    L.mwx_stt_align_pcm16.restype = C.c_int
+    L.mwx_stt_align_pcm16.argtypes = [C.c_void_p, C.POINTER(C.c_int16), C.c_int, C.c_int,
+                                      C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
+    return L
+
+
+def _align_json(r: dict) -> dict:
+    f32 = lambda u: float(np.array([u], np.uint32).view(np.float32)[0])
+    unhex = lambda s: bytes.fromhex(s).decode("utf-8", "replace")
+    out = dict(ok=bool(r["ok"]), text=unhex(r["text"]), language=unhex(r["language"]),
+               avg_logprob=f32(r["avg_logprob"]), eot_logprob=f32(r["eot_logprob"]),
+               n_agree=r["n_agree"], tokens=[])
+    for t in r["tokens"]:
+        out["tokens"].append(dict(id=t["id"], p=f32(t["p"]), plog=f32(t["plog"]), t=t["t"],
+                                  top_id=t["top_id"], top_plog=f32(t["top_plog"]),
+                                  text=unhex(t["text"]), top_text=unhex(t["top_text"])))
+    return out
+
+
+def stt_align_pcm16(L: C.CDLL, eng, pcm16: np.ndarray, sample_rate: int, text: str,
+                    language: str = "", translate: bool = False) -> dict:
+    """SttEngine::align_pcm16 through mwx_stt_align_pcm16: the AlignmentResult
+    as a dict (floats exact: they cross as f32 bit patterns)."""
+    import json
+    pcm16 = np.ascontiguousarray(pcm16, dtype=np.int16)
+    cap = 1 << 20
+    buf = C.create_string_buffer(cap)
+    rc = L.mwx_stt_align_pcm16(eng, pcm16.ctypes.data_as(C.POINTER(C.c_int16)), len(pcm16),
+                               sample_rate, text.encode(), language.encode(), int(translate), buf,
+                               cap)
+    if rc < 0:
+        raise RuntimeError(f"mwx_stt_align_pcm16 failed ({rc})")
+    return _align_json(json.loads(buf.value.decode()))
+
+
 def dequantize(qtype: int, raw: bytes, n: int) -> np.ndarray:
     """mwx_test_dequantize: the engine's load-time dequantizer (host only)."""
     out = np.empty(n, np.float32)
@@ -728,6 +779,73 @@ class Context:
 
     def lang_id(self, state_index: int = 0) -> int:
         return lib().mwx_full_lang_id_from_state(self.state(state_index))
+
+    # ---- transcript alignment (mwx.h mwx_align_batch) ----
+    def align_batch(self, pcms: Sequence[np.ndarray], tokens: Sequence[Sequence[int]],
+                    params: FullParams, state_indices: Optional[Sequence[int]] = None) -> int:
+        """mwx_align_batch: clip b and its text tokens on state state_indices[b]
+        (default b). Returns the call's code; segments() / align_rows() read
+        the result."""
+        n = len(pcms)
+        idx = list(range(n)) if state_indices is None else list(state_indices)
+        arrs = [np.ascontiguousarray(p, dtype=np.float32) for p in pcms]
+        toks = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in tokens]
+        states = (C.c_void_p * n)(*[self.state(i) for i in idx])
+        ptrs = (C.POINTER(C.c_float) * n)(*[fptr(a) for a in arrs])
+        lens = (C.c_int * n)(*[len(a) for a in arrs])
+        ip = C.POINTER(C.c_int32)
+        tptr = (ip * n)(*[t.ctypes.data_as(ip) for t in toks])
+        tlen = (C.c_int * n)(*[len(t) for t in toks])
+        self._keep = (arrs, toks)
+        fn = lib().mwx_align_batch
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), FullParams,
+                       C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int), C.POINTER(ip),
+                       C.POINTER(C.c_int), C.c_int]
+        return fn(self.ctx, states, params, ptrs, lens, tptr, tlen, n)
+
+    def align_rows(self, state_index: int = 0) -> np.ndarray:
+        """The rows of the state's last align_batch (mwx_align_row): a record
+        array of SCORE_OUT without p, n + 1 rows (the last one: EOT); empty
+        when the state has none."""
+        fn = lib().mwx_align_row
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                       C.POINTER(C.c_float)]
+        s = self.state(state_index)
+        rows = []
+        while True:
+            plog, top, tplog = C.c_float(), C.c_int32(), C.c_float()
+            if fn(s, len(rows), C.byref(plog), C.byref(top), C.byref(tplog)) != 0:
+                break
+            rows.append((plog.value, top.value, tplog.value))
+        return np.array(rows, dtype=[("plog", np.float32), ("top_id", np.int32),
+                                     ("top_plog", np.float32)])
+
+    def test_score_rows_rc(self, logits: np.ndarray, target, active):
+        """mwx_test_score_rows: logits [R][V] f32, target [R], active [R].
+        Returns (rc, plog, p, top_id, top_plog), [R] each; what the launch did
+        not write is NaN (top_id: -1)."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        R, V = logits.shape
+        target = np.ascontiguousarray(target, dtype=np.int32)
+        active = np.ascontiguousarray(active, dtype=np.int32)
+        assert target.shape == (R,) and active.shape == (R,)
+        plog, p, tplog = (np.full(R, np.nan, np.float32) for _ in range(3))
+        top = np.full(R, -1, np.int32)
+        fn = lib().mwx_test_score_rows
+        fpp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, fpp, ip, ip, fpp, fpp, ip, fpp]
+        rc = fn(self.ctx, R, V, fptr(logits), target.ctypes.data_as(ip), active.ctypes.data_as(ip),
+                fptr(plog), fptr(p), top.ctypes.data_as(ip), fptr(tplog))
+        return rc, plog, p, top, tplog
+
+    def test_score_rows(self, logits, target, active):
+        """As test_score_rows_rc, raising on a non-zero return."""
+        rc, *res = self.test_score_rows_rc(logits, target, active)
+        self._hook_rc("mwx_test_score_rows", rc)
+        return tuple(res)
 
     # ---- per-stage test entry points ----
     def hparam(self, name: str) -> int:
