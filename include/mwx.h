@@ -241,7 +241,27 @@ struct mwx_full_params {
    * effect of a short context on recognition quality is unmeasured (no real
    * checkpoint has been run with it): opt-in. */
   bool audio_ctx_fit;
+
+  /* Engine extension (appended field): NULL (default), or one language id per
+   * batch entry. Entry b with lang_ids[b] >= 0 is transcribed in that language
+   * (mwx_lang_str(lang_ids[b])): it takes no part in the detection pass and is
+   * not encoded for it, and its result is bit-identical to the same clip run
+   * alone with that language, whatever else is in the batch. Entry b with
+   * lang_ids[b] < 0 follows `language`. An id above mwx_lang_max_id(): the
+   * call returns -3 before any GPU work. A non-multilingual model ignores the
+   * field, as it ignores `language`. Honoured by mwx_full_batch, _pcm16,
+   * _trimmed, _chunked (every chunk of entry b gets lang_ids[b]) and
+   * mwx_align_batch; mwx_full_with_state reads lang_ids[0]. */
+  const int* lang_ids;
+
+  /* Engine extension (appended field), read by mwx_full_batch_chunked only and
+   * only for entries whose language is to be detected: MWX_CHUNK_LANG_PER_CHUNK
+   * (0, default) detects per chunk; MWX_CHUNK_LANG_RECORDING (1) detects once
+   * per recording (rule at mwx_full_batch_chunked). */
+  int chunk_language;
 };
+#define MWX_CHUNK_LANG_PER_CHUNK 0
+#define MWX_CHUNK_LANG_RECORDING 1
 
 /* --- lifecycle --------------------------------------------------------- */
 struct mwx_context_params mwx_context_default_params(void);
@@ -298,6 +318,13 @@ int mwx_full_n_tokens_from_state(struct mwx_state* state, int i_segment);
 mwx_token_data mwx_full_get_token_data_from_state(struct mwx_state* state,
                                                   int i_segment, int i_token);
 int mwx_full_lang_id_from_state(struct mwx_state* state);
+/* Per-language probabilities of the detection pass of the last call on this
+ * state (language auto / detect_language), probs[id] for id < the return value
+ * (mwx_lang_max_id() + 1); 0 when that call did not detect; -1 bad arguments
+ * (n smaller than that). The softmax runs over the language logits only, as
+ * whisper_lang_auto_detect's does; the language used is the first maximum of
+ * those logits. */
+int mwx_full_lang_probs_from_state(struct mwx_state* state, float* probs, int n);
 
 /* --- segment prosody -----------------------------------------------------
  * The reference's per-segment affect / speaker features
@@ -636,7 +663,20 @@ int mwx_vad_last_chunk_kernel_ms(struct mwx_vad_context* vctx, float* chunks_ms)
  * max_batch. params.offset_ms and params.duration_ms must be 0 (-1, logged).
  * On an error or an abort (polled between runs too) the code is returned and
  * every state of the call holds 0 segments. For an object made by
- * mwx_vad_trim_batch this is mwx_full_batch_trimmed. */
+ * mwx_vad_trim_batch this is mwx_full_batch_trimmed.
+ *
+ * params.chunk_language = MWX_CHUNK_LANG_RECORDING (this project's definition,
+ * DESIGN.md D13): for every entry whose language is to be detected, its
+ * leading chunks 0..k, k the smallest index at which their summed length
+ * reaches 480000 samples (all chunks if they never do), those shorter than
+ * 0.1 s left out, first go through a detection-only pass (runs of at most
+ * max_batch, in (entry, chunk) order). Their probabilities are pooled,
+ * P = sum_j len_j p_j / sum_j len_j (double, in chunk order); the recording's
+ * language is the lowest id among the maxima of P, and every chunk of the
+ * entry is then transcribed in it (lang_ids). states[b] ends with that
+ * language id and with P, rounded to float, as its lang_probs. An entry with
+ * no chunk of at least 0.1 s ends as with MWX_CHUNK_LANG_PER_CHUNK. At most
+ * about 30 s of speech per recording is encoded twice. */
 int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* states,
                            struct mwx_full_params params,
                            const struct mwx_vad_trimmed* const* trimmed, const int* clip_index,

@@ -441,6 +441,27 @@ int mwx_test_score_rows(struct mwx_context* ctx, int R, int V, const float* logi
  * depend on it. */
 int mwx_test_set_score_rows_cap(int rows);
 
+/* --- language identification (tests/test_gpu_lang_kernel.py, _detect.py) --- */
+
+/* One lang_probs launch (csrc/k_lang.hip, DESIGN.md "Language identification")
+ * on R rows of V raw logits [R][V], over the n entries from t0 of each row.
+ * Out: probs [R][n], best [R]. The hook owns the device buffers; both outputs
+ * lie between two guard bands of sentinel words. Returns 0; -1 without a
+ * launch, the outputs untouched, for a null argument, R <= 0, n outside
+ * 1..128, t0 < 0 or t0 + n > V; -2 on a device error; -3 if the launch changed
+ * a guard band. */
+int mwx_test_lang_probs(struct mwx_context* ctx, int R, int V, const float* logits, int t0, int n,
+                        float* probs, int* best);
+
+/* A state keeps (on != 0) the language-logit row that the detection pass of
+ * its next mwx_full* / mwx_align_batch calls feeds lang_probs for it. Returns
+ * the previous setting. */
+int mwx_test_lang_keep(struct mwx_state* state, int on);
+/* That row of the state's last call: mwx_lang_max_id() + 1 raw logits into
+ * logits_out (room for n). Returns their number; 0 when the call kept none
+ * (no detection for this state, or keeping off); -1 bad arguments. */
+int mwx_test_lang_last(struct mwx_state* state, float* logits_out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -408,7 +408,17 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
   for (int c = 0; c < n_clips; ++c) {
     states[c]->s.result_all.clear();
     states[c]->s.dtw_dump.clear();
+    states[c]->s.lang_probs.clear();
+    states[c]->s.lang_last.clear();
   }
+  // per-entry languages (mwx.h: lang_ids): fixed_lang[c] >= 0 is clip c's
+  // language, whatever P.language says; such a clip takes no part in detection
+  std::vector<int> fixed_lang(n_clips, -1);
+  if (P.lang_ids && vb.is_multilingual())
+    for (int c = 0; c < n_clips; ++c) {
+      if (P.lang_ids[c] > lang_max_id()) return -3;
+      if (P.lang_ids[c] >= 0) fixed_lang[c] = P.lang_ids[c];
+    }
   if (P.audio_ctx > hp.n_audio_ctx) return -5;
   if (P.audio_ctx < 0) P.audio_ctx = 0;
   const bool beam = P.strategy == MWX_SAMPLING_BEAM_SEARCH;
@@ -548,10 +558,15 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
     return 0;
   };
   std::vector<std::string> lang_of_clip(n_clips, P.language ? P.language : "");
+  for (int c = 0; c < n_clips; ++c)
+    if (fixed_lang[c] >= 0) {
+      clips[c].lang_id = fixed_lang[c];
+      lang_of_clip[c] = lang_str(fixed_lang[c]);
+    }
   if (detect) {
     std::vector<int> which, seeks;
     for (int c = 0; c < n_clips; ++c) {
-      if (clips[c].n_len_org <= 0) continue;
+      if (clips[c].n_len_org <= 0 || fixed_lang[c] >= 0) continue;
       which.push_back(c);
       seeks.push_back(0);
     }
@@ -580,7 +595,26 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
         HIPC(hipMemcpyAsync(ll.data() + (size_t)r * nl,
                             (float*)S.logits.p + (size_t)r * V + vb.token_sot + 1, nl * 4,
                             hipMemcpyDeviceToHost, st));
+      // the per-language distribution of the same rows (k_lang.hip), kept per
+      // clip; the language used stays the host's choice from `ll` below
+      std::vector<float> lp((size_t)R * nl);
+      {
+        float* d_lp = (float*)S.lg_probs.get((size_t)R * nl * 4);
+        int* d_lb = (int*)S.lg_best.get((size_t)R * 4);
+        {
+          PerfScope ps(S, "lang");
+          if (!lang_probs((const float*)S.logits.p, R, V, vb.token_sot + 1, nl, d_lp, d_lb, st))
+            return -1;
+        }
+        HIPC(hipMemcpyAsync(lp.data(), d_lp, lp.size() * 4, hipMemcpyDeviceToHost, st));
+      }
       HIPC(hipStreamSynchronize(st));
+      for (int r = 0; r < R; ++r) {
+        State& cs = states[which[r]]->s;
+        cs.lang_probs.assign(lp.begin() + (size_t)r * nl, lp.begin() + (size_t)(r + 1) * nl);
+        if (cs.lang_keep)
+          cs.lang_last.assign(ll.begin() + (size_t)r * nl, ll.begin() + (size_t)(r + 1) * nl);
+      }
       for (int r = 0; r < R; ++r) {
         std::vector<std::pair<float, int>> lid;
         for (const auto& kv : lang_table_sorted())
@@ -1775,6 +1809,8 @@ struct mwx_full_params mwx_full_default_params(int strategy) {
   p.max_tokens = 0;
   p.audio_ctx = 0;
   p.audio_ctx_fit = false;
+  p.lang_ids = nullptr;
+  p.chunk_language = MWX_CHUNK_LANG_PER_CHUNK;
   p.tdrz_enable = false;
   p.initial_prompt = nullptr;
   p.prompt_tokens = nullptr;
@@ -1805,12 +1841,32 @@ struct mwx_full_params mwx_full_default_params(int strategy) {
   return p;
 }
 
+namespace mwx {
+// mwx_full_params.lang_ids of a call with n entries: no id above lang_max_id()
+// (a non-multilingual model ignores the field)
+// One language per recording (mwx_full_batch_chunked, DESIGN.md D13): chunks
+// are pooled until their summed length reaches kLangPoolSamples; a chunk
+// counts when the engine would decode it (ten mel frames: the 0.1-s rule of
+// run_full's window loop)
+constexpr int64_t kLangPoolSamples = 30 * MWX_SAMPLE_RATE;
+static bool lang_chunk_counts(int len) {
+  return len > 0 && 1 + (len + 200 - 400) / MWX_HOP_LENGTH >= 10;
+}
+static bool lang_ids_ok(const Vocab& vb, const int* lang_ids, int n) {
+  if (!lang_ids || !vb.is_multilingual()) return true;
+  for (int b = 0; b < n; ++b)
+    if (lang_ids[b] > lang_max_id()) return false;
+  return true;
+}
+}  // namespace mwx
+
 static int full_batch_any(struct mwx_context* ctx, struct mwx_state* const* states,
                           struct mwx_full_params params, const void* const* samples,
                           const int* n_samples, int n_clips, bool pcm16) {
   if (!ctx || !states || n_clips <= 0) return -1;
   for (int c = 0; c < n_clips; ++c)
     if (!states[c] || (n_samples[c] > 0 && !samples[c])) return -1;
+  if (!mwx::lang_ids_ok(ctx->c.vocab, params.lang_ids, n_clips)) return -3;
   try {
     HIPC(hipSetDevice(ctx->c.device));
     if (ctx->c.wtype == mwx::GGML_BF16)
@@ -1872,8 +1928,10 @@ int mwx_align_batch(struct mwx_context* ctx, struct mwx_state* const* states,
     for (int j = 0; j < n_tokens[c]; ++j)
       if (tokens[c][j] < 0 || tokens[c][j] >= vb.token_eot) return -3;
   if (params.audio_ctx > hp.n_audio_ctx) return -5;
+  if (!mwx::lang_ids_ok(vb, params.lang_ids, n_clips)) return -3;
   mwx_full_params P = mwx_full_default_params(MWX_SAMPLING_GREEDY);
   P.language = params.language;
+  P.lang_ids = params.lang_ids;
   P.translate = params.translate;
   P.audio_ctx = params.audio_ctx;
   P.audio_ctx_fit = params.audio_ctx_fit;
@@ -1927,16 +1985,22 @@ int mwx_full_batch_trimmed(struct mwx_context* ctx, struct mwx_state* const* sta
     }
     if (t->clips[clip_index[b]].n_compact > 0x7fffffffLL) return -1;
   }
+  if (!mwx::lang_ids_ok(ctx->c.vocab, params.lang_ids, n_clips)) return -3;
+  std::vector<int> run_ids;  // (each kept entry's language id travels with it)
   for (int b = 0; b < n_clips; ++b) {
     const mwx_vad_trimmed::Clip& c = trimmed[b]->clips[clip_index[b]];
     states[b]->s.result_all.clear();
+    states[b]->s.lang_probs.clear();
+    states[b]->s.lang_last.clear();
     if (c.seg.empty() || c.n_compact <= 0) continue;
+    if (params.lang_ids) run_ids.push_back(params.lang_ids[b]);
     run_states.push_back(states[b]);
     ptrs.push_back(trimmed[b]->d_pcm + c.off);
     lens.push_back((int)c.n_compact);
     run_clips.push_back(&c);
   }
   if (run_states.empty()) return 0;
+  if (params.lang_ids) params.lang_ids = run_ids.data();
   const int rc = full_batch_any(ctx, run_states.data(), params, ptrs.data(), lens.data(),
                                 (int)run_states.size(), false);
   if (rc != 0) return rc;
@@ -1972,7 +2036,11 @@ int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* sta
   };
   std::vector<Job> jobs;
   for (int b = 0; b < n_clips; ++b)  // (an error below leaves every state with 0 segments)
-    if (states[b]) states[b]->s.result_all.clear();
+    if (states[b]) {
+      states[b]->s.result_all.clear();
+      states[b]->s.lang_probs.clear();
+      states[b]->s.lang_last.clear();
+    }
   for (int b = 0; b < n_clips; ++b) {
     const mwx_vad_trimmed* t = trimmed[b];
     if (!states[b] || !t || clip_index[b] < 0 || (size_t)clip_index[b] >= t->clips.size())
@@ -1988,6 +2056,7 @@ int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* sta
     MWX_LOG_ERROR("mwx_full_batch_chunked: offset_ms and duration_ms must be 0\n");
     return -1;
   }
+  if (!mwx::lang_ids_ok(ctx->c.vocab, params.lang_ids, n_clips)) return -3;
   for (int b = 0; b < n_clips; ++b) {
     const mwx_vad_trimmed::Clip& c = trimmed[b]->clips[clip_index[b]];
     if (c.seg.empty() || c.n_compact <= 0) continue;
@@ -2011,7 +2080,76 @@ int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* sta
   run_states.insert(run_states.end(), s0->scratch.begin(), s0->scratch.begin() + (width - 1));
   std::vector<std::vector<mwx::Segment>> acc((size_t)n_clips);
   std::vector<int> lang((size_t)n_clips, -1);
+  std::vector<std::vector<float>> lprobs((size_t)n_clips);
   int rc = 0;
+  // every chunk of entry b runs with entry_lang[b] (-1: params.language)
+  const bool ml = ctx->c.vocab.is_multilingual();
+  std::vector<int> entry_lang((size_t)n_clips, -1);
+  if (ml && params.lang_ids)
+    for (int b = 0; b < n_clips; ++b) entry_lang[b] = std::max(-1, params.lang_ids[b]);
+  // one language per recording (mwx.h; DESIGN.md D13): a detection-only pass
+  // over each such entry's leading chunks, pooled by length
+  const bool auto_lang = params.language == nullptr || strlen(params.language) == 0 ||
+                         strcmp(params.language, "auto") == 0;
+  std::vector<char> pooled((size_t)n_clips, 0);
+  if (ml && auto_lang && !params.detect_language &&
+      params.chunk_language == MWX_CHUNK_LANG_RECORDING) {
+    std::vector<size_t> det;  // (indices into jobs, in (entry, chunk) order)
+    std::vector<int64_t> cum((size_t)n_clips, 0);
+    for (size_t i = 0; i < jobs.size(); ++i) {
+      const Job& jb = jobs[i];
+      if (entry_lang[jb.entry] >= 0 || cum[jb.entry] >= mwx::kLangPoolSamples) continue;
+      if (!mwx::lang_chunk_counts(jb.len)) continue;
+      det.push_back(i);
+      cum[jb.entry] += jb.len;
+    }
+    const int nl = mwx::lang_max_id() + 1;
+    std::vector<std::vector<double>> psum((size_t)n_clips);
+    mwx_full_params pd = params;
+    pd.detect_language = true;
+    pd.lang_ids = nullptr;
+    for (size_t r0 = 0; r0 < det.size(); r0 += width) {
+      const size_t n = std::min(width, det.size() - r0);
+      if (r0 > 0 && mwx::aborted(params)) {
+        rc = -9;
+        break;
+      }
+      std::vector<const void*> ptrs;
+      std::vector<int> lens;
+      for (size_t i = 0; i < n; ++i) {
+        ptrs.push_back(jobs[det[r0 + i]].pcm);
+        lens.push_back(jobs[det[r0 + i]].len);
+      }
+      rc = full_batch_any(ctx, run_states.data(), pd, ptrs.data(), lens.data(), (int)n, false);
+      if (rc != 0) break;
+      for (size_t i = 0; i < n; ++i) {
+        const Job& jb = jobs[det[r0 + i]];
+        const std::vector<float>& p = run_states[i]->s.lang_probs;
+        if ((int)p.size() != nl) {
+          rc = -1;
+          break;
+        }
+        std::vector<double>& a = psum[jb.entry];
+        a.resize((size_t)nl, 0.0);
+        for (int k = 0; k < nl; ++k) a[k] += (double)jb.len * (double)p[k];
+      }
+      if (rc != 0) break;
+    }
+    if (rc == 0 && !det.empty() && mwx::aborted(params)) rc = -9;
+    for (int b = 0; b < n_clips && rc == 0; ++b) {
+      if (psum[b].empty()) continue;
+      lprobs[b].resize((size_t)nl);
+      int best = 0;
+      for (int k = 0; k < nl; ++k) {
+        lprobs[b][k] = (float)(psum[b][k] / (double)cum[b]);
+        if (lprobs[b][k] > lprobs[b][best]) best = k;
+      }
+      entry_lang[b] = best;
+      pooled[b] = 1;
+    }
+  }
+  bool any_lang = false;
+  for (int b = 0; b < n_clips; ++b) any_lang = any_lang || entry_lang[b] >= 0;
   for (size_t r0 = 0; r0 < jobs.size() && rc == 0; r0 += width) {
     const size_t n = std::min(width, jobs.size() - r0);
     if (r0 > 0 && mwx::aborted(params)) {
@@ -2019,12 +2157,15 @@ int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* sta
       break;
     }
     std::vector<const void*> ptrs;
-    std::vector<int> lens;
+    std::vector<int> lens, ids;
     for (size_t i = 0; i < n; ++i) {
       ptrs.push_back(jobs[r0 + i].pcm);
       lens.push_back(jobs[r0 + i].len);
+      ids.push_back(entry_lang[jobs[r0 + i].entry]);
     }
-    rc = full_batch_any(ctx, run_states.data(), params, ptrs.data(), lens.data(), (int)n, false);
+    mwx_full_params pr = params;
+    pr.lang_ids = any_lang ? ids.data() : nullptr;
+    rc = full_batch_any(ctx, run_states.data(), pr, ptrs.data(), lens.data(), (int)n, false);
     if (rc != 0) break;
     for (size_t i = 0; i < n; ++i) {
       const Job& jb = jobs[r0 + i];
@@ -2040,16 +2181,23 @@ int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* sta
         acc[jb.entry].push_back(std::move(sg));
       }
       rs.result_all.clear();
-      if (jb.chunk == 0) lang[jb.entry] = rs.lang_id;
+      if (jb.chunk == 0) {
+        lang[jb.entry] = rs.lang_id;
+        if (!pooled[jb.entry]) lprobs[jb.entry] = rs.lang_probs;
+      }
     }
   }
-  for (mwx_state* rs : run_states) rs->s.result_all.clear();
+  for (mwx_state* rs : run_states) {
+    rs->s.result_all.clear();
+    rs->s.lang_probs.clear();
+  }
   for (int b = 0; b < n_clips; ++b) states[b]->s.result_all.clear();
   if (rc != 0) return rc;
   for (int b = 0; b < n_clips; ++b) {
     if (lang[b] < 0) continue;
     states[b]->s.result_all = std::move(acc[b]);
-    states[b]->s.lang_id = lang[b];
+    states[b]->s.lang_id = pooled[b] ? entry_lang[b] : lang[b];
+    states[b]->s.lang_probs = std::move(lprobs[b]);
   }
   return 0;
 }
@@ -2319,6 +2467,13 @@ mwx_token_data mwx_full_get_token_data_from_state(struct mwx_state* state, int i
   return state->s.result_all.at(i).tokens.at(j);
 }
 int mwx_full_lang_id_from_state(struct mwx_state* state) { return state ? state->s.lang_id : -1; }
+int mwx_full_lang_probs_from_state(struct mwx_state* state, float* probs, int n) {
+  if (!state || !probs || n < mwx::lang_max_id() + 1) return -1;
+  const std::vector<float>& lp = state->s.lang_probs;
+  if (lp.empty()) return 0;
+  memcpy(probs, lp.data(), lp.size() * 4);
+  return (int)lp.size();
+}
 
 const char* mwx_token_to_str(struct mwx_context* ctx, mwx_token token) {
   return ctx->c.vocab.id_to_token.at(token).c_str();
@@ -3884,4 +4039,50 @@ extern "C" int mwx_test_score_rows(struct mwx_context* ctx, int R, int V, const 
 
 extern "C" int mwx_test_set_score_rows_cap(int rows) {
   return mwx::score_rows_cap_var().exchange(rows > 0 ? rows : mwx::kScoreRowsCap);
+}
+
+// ---------------------------------------------------------------------------
+// Language identification on given data (k_lang.hip), and the detection
+// pass's kept logit row
+// ---------------------------------------------------------------------------
+extern "C" int mwx_test_lang_probs(struct mwx_context* ctx, int R, int V, const float* logits,
+                                   int t0, int n, float* probs, int* best) {
+  if (!ctx || !logits || !probs || !best) return -1;
+  if (R <= 0 || n < 1 || n > mwx::LANG_MAX_N || t0 < 0 || (long)t0 + n > V) return -1;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    const size_t rv = (size_t)R * V * 4;
+    DevScratch m;
+    float* dl = (float*)m.get(rv);
+    HIPC(hipMemcpy(dl, logits, rv, hipMemcpyHostToDevice));
+    GuardedBuf gp, gb;
+    float* dp = (float*)gp.make(m, (size_t)R * n * 4, nullptr);
+    int* db = (int*)gb.make(m, (size_t)R * 4, nullptr);
+    if (!mwx::lang_probs(dl, R, V, t0, n, dp, db, nullptr)) return -1;
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    std::vector<float> hp((size_t)R * n);
+    std::vector<int> hb((size_t)R);
+    if (!gp.take(hp.data()) || !gb.take(hb.data())) return -3;
+    memcpy(probs, hp.data(), hp.size() * 4);
+    memcpy(best, hb.data(), hb.size() * 4);
+    return 0;
+  } catch (...) {
+    return -2;
+  }
+}
+
+extern "C" int mwx_test_lang_keep(struct mwx_state* state, int on) {
+  if (!state) return -1;
+  const int prev = state->s.lang_keep ? 1 : 0;
+  state->s.lang_keep = on != 0;
+  if (!on) state->s.lang_last.clear();
+  return prev;
+}
+
+extern "C" int mwx_test_lang_last(struct mwx_state* state, float* logits_out, int n) {
+  if (!state || !logits_out || n < mwx::lang_max_id() + 1) return -1;
+  const std::vector<float>& ll = state->s.lang_last;
+  if (!ll.empty()) memcpy(logits_out, ll.data(), ll.size() * 4);
+  return (int)ll.size();
 }

@@ -309,6 +309,14 @@ struct State {
   std::vector<DtwDump> dtw_dump;
   std::vector<Segment> result_all;
   int lang_id = 0;
+  // language identification: the detection pass's probabilities [R][n] and
+  // best [R] on the device (the state that runs the batch), and per clip's
+  // state the probabilities of its last call (empty when that call did not
+  // detect for it); with lang_keep, also the logit row the kernel read
+  DBuf lg_probs, lg_best;
+  std::vector<float> lang_probs;
+  bool lang_keep = false;
+  std::vector<float> lang_last;
   std::mt19937 rng0 = std::mt19937(0);  // decoders[0].rng persists per state
   // sampling / beam search: u of every draw (host RNG) in, draws out
   DBuf du, dnd, ddraw, dneed;

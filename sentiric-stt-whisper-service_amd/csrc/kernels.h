@@ -476,6 +476,17 @@ struct ScoreOut {
 bool score_rows(const float* logits, const int* target, const int* active, int R, int V,
                 ScoreOut* out, hipStream_t st);
 
+// Language identification (k_lang.hip, DESIGN.md "Language identification"):
+// for every row r, over the n entries x = logits + r V + t0 only:
+// probs[r][i] = expf(x_i - max x) / sum_j expf(x_j - max x) (-inf gives exactly
+// 0), best[r] = the lowest i among the bit-equal maxima of x. One wave per row
+// and a fixed combine order: a row's bits do not depend on R or on the row's
+// position. false (no launch) for R <= 0, n outside 1..LANG_MAX_N, t0 < 0 or
+// t0 + n > V.
+constexpr int LANG_MAX_N = 128;
+bool lang_probs(const float* logits, int R, int V, int t0, int n, float* probs, int* best,
+                hipStream_t st);
+
 // std::discrete_distribution draws from the probs rows (k_misc.hip):
 // out[row][d] for d < ndraw[row] (<= KD <= 16), u[row][d] =
 // generate_canonical<double, 53> of the row's RNG.

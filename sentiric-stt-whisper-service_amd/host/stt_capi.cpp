@@ -35,6 +35,8 @@ std::string to_json(const std::vector<TranscriptionResult>& rs) {
                   r.token_count);
     o += buf;
     o += "\"text\":\"" + hex(r.text) + "\",\"language\":\"" + hex(r.language) + "\",";
+    std::snprintf(buf, sizeof buf, "\"language_probability\":%.9g,", r.language_probability);
+    o += buf;
     const AffectiveTags& a = r.affective;
     std::snprintf(buf, sizeof buf,
                   "\"gender\":\"%s\",\"emotion\":\"%s\",\"speaker\":\"%s\",\"arousal\":%.9g,"
@@ -449,6 +451,50 @@ int mwx_stt_set_vad_chunk(void* eng, float chunk_s, int chunk_batch) {
   SttEngine* e = static_cast<SttEngine*>(eng);
   if (!e->set_vad_chunk(chunk_s, chunk_batch)) return -1;
   return e->chunk_active() ? 1 : 0;
+}
+
+// Settings::chunk_language_recording (one language per recording on the
+// chunked path) of the requests that start after the call. 0;
+// -1 without an engine.
+int mwx_stt_set_chunk_language_recording(void* eng, int on) {
+  if (!eng) return -1;
+  static_cast<SttEngine*>(eng)->set_chunk_language_recording(on != 0);
+  return 0;
+}
+
+// SttEngine::detect_language_pcm16 / detect_language: a JSON list of
+// {"language": hex, "p": f32 bits}, best first. Return codes as
+// mwx_stt_transcribe_pcm16.
+static int detect_any(void* eng, const float* f, const int16_t* s, int n, int sample_rate,
+                      int top_k, char* out, int cap) {
+  try {
+    SttEngine* e = static_cast<SttEngine*>(eng);
+    const auto r = f ? e->detect_language(std::vector<float>(f, f + n), sample_rate, top_k)
+                     : e->detect_language_pcm16(std::vector<int16_t>(s, s + n), sample_rate, top_k);
+    std::string j = "[";
+    char buf[64];
+    for (size_t i = 0; i < r.size(); ++i) {
+      std::snprintf(buf, sizeof buf, "\",\"p\":%u}", f32_bits(r[i].second));
+      j += std::string(i ? "," : "") + "{\"language\":\"" + hex(r[i].first) + buf;
+    }
+    j += "]";
+    const int rc = emit(j, out, cap);
+    return rc < -1 ? rc - 2 : rc;
+  } catch (const EngineBusyException&) {
+    return -2;
+  } catch (...) {
+    return -1;
+  }
+}
+int mwx_stt_detect_language(void* eng, const float* pcm, int n, int sample_rate, int top_k,
+                            char* out, int cap) {
+  if (!eng || !pcm || n < 0) return -1;
+  return detect_any(eng, pcm, nullptr, n, sample_rate, top_k, out, cap);
+}
+int mwx_stt_detect_language_pcm16(void* eng, const int16_t* pcm, int n, int sample_rate, int top_k,
+                                  char* out, int cap) {
+  if (!eng || !pcm || n < 0) return -1;
+  return detect_any(eng, nullptr, pcm, n, sample_rate, top_k, out, cap);
 }
 
 // 0.. = JSON length written; -1 = error; -2 = EngineBusyException;

@@ -49,6 +49,10 @@
 #pragma weak mwx_tokenize
 #pragma weak mwx_full_lang_id_from_state
 #pragma weak mwx_lang_str
+// ... and the language-probability calls: without them detect_language()
+// returns nothing and language_probability stays -1
+#pragma weak mwx_full_lang_probs_from_state
+#pragma weak mwx_lang_max_id
 
 namespace mwx_host {
 
@@ -216,6 +220,8 @@ SttEngine::SttEngine(const Settings& settings) : settings_(settings) {
   all_states_.push_back(aux_state_);
   align_bound_ = mwx_align_batch && mwx_align_row && mwx_tokenize && mwx_full_lang_id_from_state &&
                  mwx_lang_str;
+  lang_bound_ = mwx_full_lang_probs_from_state && mwx_lang_max_id && mwx_lang_str &&
+                mwx_full_lang_id_from_state;
   // src/stt_engine.cpp:44-55: a VAD model that does not load is logged and the
   // engine carries on without the gate
   if (settings_.enable_vad) {
@@ -482,6 +488,8 @@ mwx_full_params SttEngine::make_params(const RequestOptions& options, std::strin
   p.n_threads = settings_.n_threads;
   p.audio_ctx = settings_.audio_ctx;
   p.audio_ctx_fit = settings_.audio_ctx_fit;
+  p.chunk_language =
+      settings_.chunk_language_recording ? MWX_CHUNK_LANG_RECORDING : MWX_CHUNK_LANG_PER_CHUNK;
   return p;
 }
 
@@ -492,6 +500,14 @@ std::vector<TranscriptionResult> SttEngine::collect(mwx_state* state, const std:
                                                     int* token_count) const {
   std::vector<TranscriptionResult> results;
   std::vector<int64_t> seg_start, seg_len;
+  // the used language's probability, when the call's detection pass ran
+  float lang_prob = -1.0f;
+  if (lang_bound_) {
+    std::vector<float> probs((size_t)mwx_lang_max_id() + 1);
+    const int n = mwx_full_lang_probs_from_state(state, probs.data(), (int)probs.size());
+    const int id = mwx_full_lang_id_from_state(state);
+    if (n > 0 && id >= 0 && id < n) lang_prob = probs[id];
+  }
   const int eot = mwx_token_eot(ctx_);
   const int n_seg = mwx_full_n_segments_from_state(state);
   for (int i = 0; i < n_seg; ++i) {
@@ -537,6 +553,7 @@ std::vector<TranscriptionResult> SttEngine::collect(mwx_state* state, const std:
     TranscriptionResult r;
     r.text = text;
     r.language = lang;
+    r.language_probability = lang_prob;
     r.prob = avg;
     r.t0 = t0;
     r.t1 = t1;
@@ -886,6 +903,70 @@ AlignmentResult SttEngine::align(const std::vector<float>& pcmf32, int sample_ra
   mwx_state* state = guard.get();
   std::vector<AlignmentResult> r = align_run(&state, {&pcm}, {text}, options);
   return r.empty() ? AlignmentResult() : std::move(r[0]);
+}
+
+// ---- language identification ------------------------------------------------
+std::vector<std::pair<std::string, float>> SttEngine::detect_language(
+    const std::vector<float>& pcmf32, int sample_rate, int top_k) {
+  if (!ctx_) return {};
+  if (!lang_bound_) {
+    std::fprintf(stderr, "SttEngine: detect_language: the library has no language-probability calls\n");
+    return {};
+  }
+  std::vector<float> resampled;
+  if (sample_rate != 16000)
+    resampled = resample_audio(pcmf32.data(), pcmf32.size(), sample_rate, 16000);
+  const std::vector<float>& pcm = resampled.empty() ? pcmf32 : resampled;
+  const size_t min_samples = static_cast<size_t>((settings_.vad_ms_min_duration * 16000) / 1000);
+  if (pcm.size() < min_samples) return {};
+  const int n_lang = mwx_lang_max_id() + 1;
+  std::vector<float> probs((size_t)n_lang);
+  auto run = [&](mwx_state* state) -> int {
+    std::string lang;
+    std::function<bool()> abort_fn = nullptr;
+    mwx_full_params p = make_params(RequestOptions(), lang, abort_fn);
+    p.language = "auto";
+    p.detect_language = true;
+    const int ret = mwx_full_with_state(ctx_, state, p, pcm.data(), static_cast<int>(pcm.size()));
+    if (ret != 0) {
+      std::fprintf(stderr, "SttEngine: detect_language failed: %d\n", ret);
+      return 0;
+    }
+    return mwx_full_lang_probs_from_state(state, probs.data(), n_lang);
+  };
+  int n = 0;
+  if (settings_.max_batch > 1) {
+    // (the pool's states belong to the batchers: a batch-call state serves)
+    std::lock_guard<std::mutex> batch_lock(batch_mutex_);
+    if (batch_states_.empty()) {
+      mwx_state* st = mwx_init_state(ctx_);
+      if (!st) return {};
+      batch_states_.push_back(st);
+      all_states_.push_back(st);
+    }
+    n = run(batch_states_[0]);
+  } else {
+    StateGuard guard(*this);
+    n = run(guard.get());
+  }
+  if (n <= 0) return {};
+  std::vector<int> order((size_t)n);
+  for (int i = 0; i < n; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return probs[a] > probs[b]; });
+  if (top_k >= 1 && top_k < n) order.resize((size_t)top_k);
+  std::vector<std::pair<std::string, float>> out;
+  for (int id : order) {
+    const char* s = mwx_lang_str(id);
+    out.emplace_back(s ? s : "", probs[id]);
+  }
+  return out;
+}
+
+std::vector<std::pair<std::string, float>> SttEngine::detect_language_pcm16(
+    const std::vector<int16_t>& pcm16, int sample_rate, int top_k) {
+  std::vector<float> f(pcm16.size());
+  for (size_t i = 0; i < pcm16.size(); ++i) f[i] = static_cast<float>(pcm16[i]) / 32768.0f;
+  return detect_language(f, sample_rate, top_k);
 }
 
 AlignmentResult SttEngine::align_pcm16(const std::vector<int16_t>& pcm16, int sample_rate,

@@ -112,6 +112,12 @@ struct Settings {
   // sessions do not chunk.
   float vad_chunk_s = 0.0f;
   int vad_chunk_batch = 32;
+  // One language per recording on the chunked path: with
+  // language "auto", the language is detected once over the recording's
+  // leading chunks (about 30 s of speech, pooled by length) and every chunk is
+  // transcribed in it (mwx_full_params.chunk_language =
+  // MWX_CHUNK_LANG_RECORDING). Off: every chunk detects its own language.
+  bool chunk_language_recording = false;
   // Streaming VAD for StreamSession (INTEGRATION.md "Streaming"),
   // both off by default and inert without a loaded VAD model or against a
   // library that lacks the mwx_vad_stream_* calls.
@@ -223,6 +229,9 @@ struct TranscriptionResult {
   float valence = 0.0f;
   AffectiveTags affective;
   std::string speaker_id;
+  // the probability the detection pass gave the language used (language
+  // "auto"), -1 when the call did not detect
+  float language_probability = -1.0f;
 };
 
 // Transcript alignment (SttEngine::align; mwx.h mwx_align_batch, rule D12):
@@ -284,6 +293,9 @@ class SttEngine {
     settings_.vad_chunk_batch = chunk_batch;
     return true;
   }
+  // Settings::chunk_language_recording of the requests that start after the
+  // call (as set_audio_ctx: set it before serving)
+  void set_chunk_language_recording(bool on) { settings_.chunk_language_recording = on; }
   bool chunk_active() const { return trim_active_ && chunk_bound_ && settings_.vad_chunk_s > 0.0f; }
 
   struct PerformanceMetrics {
@@ -322,6 +334,18 @@ class SttEngine {
                         const RequestOptions& options);
   AlignmentResult align_pcm16(const std::vector<int16_t>& pcm16, int sample_rate,
                               const std::string& text, const RequestOptions& options);
+  // Language identification (no reference counterpart): the clip's top_k
+  // languages (code, probability), by probability descending, then by language
+  // id; top_k < 1 or above the number of languages: all of them. The audio is
+  // resampled and the minimum-duration gate applied as transcribe() does
+  // (too short: empty); no VAD gate. One detection-only engine call
+  // (detect_language) on a pooled state; only the first 30 s are looked at.
+  // Empty on any failure or against a library without the call.
+  std::vector<std::pair<std::string, float>> detect_language(const std::vector<float>& pcm,
+                                                             int sample_rate, int top_k);
+  std::vector<std::pair<std::string, float>> detect_language_pcm16(
+      const std::vector<int16_t>& pcm16, int sample_rate, int top_k);
+
   // B independent 16 kHz clips and their texts in one GPU pass, on the states
   // kept for batch calls; clips.size() != texts.size() fails every entry.
   std::vector<AlignmentResult> align_batch(const std::vector<std::vector<float>>& clips16k,
@@ -414,6 +438,7 @@ class SttEngine {
                                               int n_clips);
   bool trim_active_ = false;  // vad_trim, a VAD context and a library that has the calls
   bool chunk_bound_ = false;  // the library has the chunked calls
+  bool lang_bound_ = false;   // the library has the language-probability calls
   bool align_bound_ = false;  // the library has the alignment calls
   // mwx_align_batch on `states` and the results of its clips
   std::vector<AlignmentResult> align_run(mwx_state* const* states,

@@ -112,7 +112,12 @@ class FullParams(C.Structure):
         ("abort_callback", ABORT_CB), ("abort_callback_user_data", C.c_void_p),
         ("bench_fixed_steps", C.c_int),
         ("audio_ctx_fit", C.c_bool),
+        ("lang_ids", C.POINTER(C.c_int)),
+        ("chunk_language", C.c_int),
     ]
+
+
+CHUNK_LANG_PER_CHUNK, CHUNK_LANG_RECORDING = 0, 1
 
 
 class VadContextParams(C.Structure):
@@ -521,6 +526,28 @@ def set_score_rows_cap(rows: int = 0) -> int:
     return fn(int(rows))
 
 
+def lang_max_id() -> int:
+    fn = lib().mwx_lang_max_id
+    fn.restype = C.c_int
+    fn.argtypes = []
+    return fn()
+
+
+def lang_id(code: str) -> int:
+    fn = lib().mwx_lang_id
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p]
+    return fn(code.encode())
+
+
+def lang_str(i: int) -> str:
+    fn = lib().mwx_lang_str
+    fn.restype = C.c_char_p
+    fn.argtypes = [C.c_int]
+    s = fn(int(i))
+    return s.decode() if s else ""
+
+
 def stt_lib() -> C.CDLL:
     """libmwx_stt.so (the host SttEngine's C glue) with the alignment calls typed."""
     L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmwx_stt.so"))
@@ -531,7 +558,29 @@ def stt_lib() -> C.CDLL:
     L.mwx_stt_align_pcm16.restype = C.c_int
     L.mwx_stt_align_pcm16.argtypes = [C.c_void_p, C.POINTER(C.c_int16), C.c_int, C.c_int,
                                       C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
+    L.mwx_stt_detect_language_pcm16.restype = C.c_int
+    L.mwx_stt_detect_language_pcm16.argtypes = [C.c_void_p, C.POINTER(C.c_int16), C.c_int, C.c_int,
+                                                C.c_int, C.c_char_p, C.c_int]
+    L.mwx_stt_set_chunk_language_recording.restype = C.c_int
+    L.mwx_stt_set_chunk_language_recording.argtypes = [C.c_void_p, C.c_int]
     return L
+
+
+def stt_detect_language_pcm16(L: C.CDLL, eng, pcm16: np.ndarray, sample_rate: int,
+                              top_k: int = 0) -> List[tuple]:
+    """SttEngine::detect_language_pcm16 through mwx_stt_detect_language_pcm16:
+    [(language code, probability as np.float32)], best first (floats exact:
+    they cross as f32 bit patterns)."""
+    import json
+    pcm16 = np.ascontiguousarray(pcm16, dtype=np.int16)
+    cap = 1 << 16
+    buf = C.create_string_buffer(cap)
+    rc = L.mwx_stt_detect_language_pcm16(eng, pcm16.ctypes.data_as(C.POINTER(C.c_int16)),
+                                         len(pcm16), sample_rate, int(top_k), buf, cap)
+    if rc < 0:
+        raise RuntimeError(f"mwx_stt_detect_language_pcm16 failed ({rc})")
+    return [(bytes.fromhex(r["language"]).decode(), np.array([r["p"]], np.uint32).view(np.float32)[0])
+            for r in json.loads(buf.value.decode())]
 
 
 def _align_json(r: dict) -> dict:
@@ -682,17 +731,34 @@ class Context:
     def default_params(strategy: int = SAMPLING_GREEDY) -> FullParams:
         return lib().mwx_full_default_params(strategy)
 
-    def full(self, pcm: np.ndarray, params: FullParams, state_index: int = 0) -> int:
+    def _lang_params(self, params: FullParams, lang_ids, n: int) -> FullParams:
+        """params, or a copy of it with FullParams.lang_ids set to the n given
+        per-entry language ids (< 0: the entry follows params.language)."""
+        if lang_ids is None:
+            return params
+        ids = [int(i) for i in lang_ids]
+        assert len(ids) == n, (len(ids), n)
+        arr = (C.c_int * n)(*ids)
+        p = FullParams.from_buffer_copy(params)  # (the caller's params keeps its strings alive)
+        p.lang_ids = arr
+        self._keep_ids = arr
+        return p
+
+    def full(self, pcm: np.ndarray, params: FullParams, state_index: int = 0,
+             lang_id: Optional[int] = None) -> int:
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        params = self._lang_params(params, None if lang_id is None else [lang_id], 1)
         return lib().mwx_full_with_state(self.ctx, self.state(state_index), params, fptr(pcm),
                                          len(pcm))
 
-    def full_batch(self, pcms: Sequence[np.ndarray], params: FullParams) -> int:
-        return self.full_batch_states(pcms, params, range(len(pcms)))
+    def full_batch(self, pcms: Sequence[np.ndarray], params: FullParams, lang_ids=None) -> int:
+        return self.full_batch_states(pcms, params, range(len(pcms)), lang_ids=lang_ids)
 
-    def full_batch_pcm16(self, pcms: Sequence[np.ndarray], params: FullParams) -> int:
+    def full_batch_pcm16(self, pcms: Sequence[np.ndarray], params: FullParams,
+                         lang_ids=None) -> int:
         """mwx_full_batch_pcm16: int16 PCM converted on the device."""
         n = len(pcms)
+        params = self._lang_params(params, lang_ids, n)
         arrs = [np.ascontiguousarray(p, dtype=np.int16) for p in pcms]
         states = (C.c_void_p * n)(*[self.state(i) for i in range(n)])
         ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
@@ -701,8 +767,9 @@ class Context:
         return lib().mwx_full_batch_pcm16(self.ctx, states, params, ptrs, lens, n)
 
     def full_batch_states(self, pcms: Sequence[np.ndarray], params: FullParams,
-                          state_indices: Sequence[int]) -> int:
+                          state_indices: Sequence[int], lang_ids=None) -> int:
         n = len(pcms)
+        params = self._lang_params(params, lang_ids, n)
         arrs = [np.ascontiguousarray(p, dtype=np.float32) for p in pcms]
         states = (C.c_void_p * n)(*[self.state(i) for i in state_indices])
         ptrs = (C.POINTER(C.c_float) * n)(*[fptr(a) for a in arrs])
@@ -726,20 +793,23 @@ class Context:
         return lib().mwx_full_batch(self.ctx, states, params, ptrs, ln, n)
 
     def full_batch_trimmed(self, trimmed: Sequence["VadTrimmed"], clip_index: Sequence[int],
-                           params: FullParams, state0: int = 0) -> int:
+                           params: FullParams, state0: int = 0, lang_ids=None) -> int:
         """mwx_full_batch_trimmed: entry b = clip clip_index[b] of trimmed[b], on
         state state0 + b; the getters then return times of the original clips."""
         n = len(trimmed)
+        params = self._lang_params(params, lang_ids, n)
         states = (C.c_void_p * n)(*[self.state(state0 + i) for i in range(n)])
         objs = (C.c_void_p * n)(*[t.t for t in trimmed])
         idx = (C.c_int * n)(*clip_index)
         return lib().mwx_full_batch_trimmed(self.ctx, states, params, objs, idx, n)
 
     def full_batch_chunked(self, trimmed: Sequence["VadTrimmed"], clip_index: Sequence[int],
-                           params: FullParams, max_batch: int = 32, state0: int = 0) -> int:
+                           params: FullParams, max_batch: int = 32, state0: int = 0,
+                           lang_ids=None) -> int:
         """mwx_full_batch_chunked: as full_batch_trimmed, every chunk of every
         entry decoded as a batch entry of its own, at most max_batch per run."""
         n = len(trimmed)
+        params = self._lang_params(params, lang_ids, n)
         states = (C.c_void_p * n)(*[self.state(state0 + i) for i in range(n)])
         objs = (C.c_void_p * n)(*[t.t for t in trimmed])
         idx = (C.c_int * n)(*clip_index)
@@ -780,13 +850,47 @@ class Context:
     def lang_id(self, state_index: int = 0) -> int:
         return lib().mwx_full_lang_id_from_state(self.state(state_index))
 
+    def lang_probs(self, state_index: int = 0) -> np.ndarray:
+        """mwx_full_lang_probs_from_state: probs[id] of the detection pass of the
+        state's last call, f32 [mwx_lang_max_id() + 1]; empty when that call
+        did not detect."""
+        fn = lib().mwx_full_lang_probs_from_state
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
+        out = np.zeros(lang_max_id() + 1, np.float32)
+        n = fn(self.state(state_index), fptr(out), out.size)
+        if n < 0:
+            raise RuntimeError(f"mwx_full_lang_probs_from_state returned {n}")
+        return out[:n]
+
+    def lang_keep(self, on: bool = True, state_index: int = 0) -> None:
+        """mwx_test_lang_keep: the state keeps the language-logit row of its
+        detection passes for lang_last()."""
+        fn = lib().mwx_test_lang_keep
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int]
+        fn(self.state(state_index), 1 if on else 0)
+
+    def lang_last(self, state_index: int = 0) -> np.ndarray:
+        """mwx_test_lang_last: the raw language logits the state's last
+        detection pass fed the kernel; empty when it kept none."""
+        fn = lib().mwx_test_lang_last
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
+        out = np.zeros(lang_max_id() + 1, np.float32)
+        n = fn(self.state(state_index), fptr(out), out.size)
+        self._hook_rc("mwx_test_lang_last", min(n, 0))
+        return out[:n]
+
     # ---- transcript alignment (mwx.h mwx_align_batch, DESIGN.md D12) ----
     def align_batch(self, pcms: Sequence[np.ndarray], tokens: Sequence[Sequence[int]],
-                    params: FullParams, state_indices: Optional[Sequence[int]] = None) -> int:
+                    params: FullParams, state_indices: Optional[Sequence[int]] = None,
+                    lang_ids=None) -> int:
         """mwx_align_batch: clip b and its text tokens on state state_indices[b]
         (default b). Returns the call's code; segments() / align_rows() read
         the result."""
         n = len(pcms)
+        params = self._lang_params(params, lang_ids, n)
         idx = list(range(n)) if state_indices is None else list(state_indices)
         arrs = [np.ascontiguousarray(p, dtype=np.float32) for p in pcms]
         toks = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in tokens]
@@ -840,6 +944,30 @@ class Context:
         rc = fn(self.ctx, R, V, fptr(logits), target.ctypes.data_as(ip), active.ctypes.data_as(ip),
                 fptr(plog), fptr(p), top.ctypes.data_as(ip), fptr(tplog))
         return rc, plog, p, top, tplog
+
+    def test_lang_probs_rc(self, logits: np.ndarray, t0: int, n: int, R: Optional[int] = None,
+                           V: Optional[int] = None):
+        """mwx_test_lang_probs: logits [R][V] f32, the n entries from t0 of each
+        row. Returns (rc, probs [R][n], best [R]); what the call did not write
+        is NaN (best: -1). R and V override the array's shape (the refusals)."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        aR, aV = logits.shape
+        R = aR if R is None else R
+        V = aV if V is None else V
+        probs = np.full((max(R, 1), min(max(n, 1), 128)), np.nan, np.float32)
+        best = np.full(max(R, 1), -1, np.int32)
+        fn = lib().mwx_test_lang_probs
+        fpp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, fpp, C.c_int, C.c_int, fpp, ip]
+        rc = fn(self.ctx, R, V, fptr(logits), t0, n, fptr(probs), best.ctypes.data_as(ip))
+        return rc, probs, best
+
+    def test_lang_probs(self, logits, t0: int, n: int):
+        """As test_lang_probs_rc, raising on a non-zero return."""
+        rc, probs, best = self.test_lang_probs_rc(logits, t0, n)
+        self._hook_rc("mwx_test_lang_probs", rc)
+        return probs, best
 
     def test_score_rows(self, logits, target, active):
         """As test_score_rows_rc, raising on a non-zero return."""
