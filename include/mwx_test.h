@@ -203,6 +203,60 @@ int mwx_test_gemm_dec(struct mwx_context* ctx, int bf16, int mode, int M, int N,
                       const float* a, const float* w, const float* bias, const float* res,
                       int* ks_out, float* out);
 
+/* The rest of the decode GEMM family through the same launchers
+ * (mwx_test_gemm_dec is this hook with w8 = ln = 0 and mode 0 .. 2). In
+ * whatever context: the kernels take their operands directly.
+ * mode 3: gemm_decode<T> with EPI_GELU and pack_out (the decode FFN1
+ *   epilogue), ldc = N, N % 32 == 0, bias [N] required: T(gelu_ggml(a.w +
+ *   bias[n])) at pack_index(m, n, N) of a buffer of ceil64(M) N 16-bit words,
+ *   which starts as 0xFFFF words; out16 receives all of it, out the rows
+ *   < M unpacked and widened to f32 [M][N].
+ * w8 != 0: MX-fp8 weights instead of w: e4m3 codes wq [N][K] and E8M0 scales
+ *   ws [N][K / 32] (any bytes), placed in fragment tiles by the model loader's
+ *   packer (mx_pack_dec_weight). bf16 only, as the engine enables them: -4
+ *   with bf16 == 0, before any launch.
+ * ln != 0 (M = 1, mode 0 or 3): the A operand is the folded LayerNorm
+ *   (gemm_splitk_ln<T> / gemm_decode_ln<T>) of x_in [K] + (the sum of the KS
+ *   slabs P [KS][K] + pbias [K]; KS = 0 .. 8, both NULL at 0), weight ln_w and
+ *   bias ln_b [K], active [1]; a is not read. x_out [K] receives the residual
+ *   buffer the launch wrote (it starts as sentinel words 0x7fc5a5a5 between
+ *   guard bands) and x_in is read back from the device after the launch. A
+ *   launcher that returns 0 / false (K not served by the fold) gives -4.
+ * ks_out (nullable): KS of mode 0, else 1. out: 8 M N floats of room in mode
+ * 0, M N otherwise. Every device output starts as sentinel words between two
+ * guard bands. Returns 0, -1 (a missing pointer, K % 32, N % 32 in mode 3,
+ * ln with M != 1 or a mode other than 0 / 3, KS outside 0 .. 8, bias / res
+ * given to a mode that takes none, M > 512, N > 4096, K > 8192), -2 (device
+ * error), -3 (a guard band changed) or -4 (shape or type not served). */
+struct mwx_test_gemm_dec_args {
+  int bf16, mode, w8, ln;
+  int M, N, K, KS;
+  const float* a;       /* [M][K] (ln == 0) */
+  const float* w;       /* [N][K] (w8 == 0) */
+  const uint8_t* wq;    /* [N][K] (w8 != 0) */
+  const uint8_t* ws;    /* [N][K / 32] */
+  const float* bias;    /* [N]: mode 2 (nullable), mode 3 */
+  const float* res;     /* [M][N]: mode 2 */
+  float* x_in;          /* ln: [K], in; read back after the launch */
+  const float* P;       /* ln: [KS][K] */
+  const float* pbias;   /* ln: [K] */
+  const float* ln_w;
+  const float* ln_b;
+  const int* active;    /* ln: [1] */
+  float* x_out;         /* ln: [K], out */
+  int* ks_out;
+  float* out;
+  uint16_t* out16;      /* mode 3: [ceil64(M) N] */
+};
+int mwx_test_gemm_dec_ex(struct mwx_context* ctx, const struct mwx_test_gemm_dec_args* args);
+
+/* The load-time MX-fp8 quantizer (mx_quantize_row; host code, no device work):
+ * x [rows][K] f32, K % 32 == 0, into e4m3fn codes q [rows][K] and E8M0 scales
+ * s [rows][K / 32]. Per 32 values: scale 2^e, e the smallest integer with
+ * amax <= 448 2^e (clamped to -127 .. 127; 0 for an all-zero block), codes
+ * the round-to-nearest-even of x / 2^e. Returns 0, or -1. */
+int mwx_test_mx_quantize_rows(const float* x, int rows, int K, uint8_t* q, uint8_t* s);
+
 /* --- encoder kernels on given data (tests/test_gpu_encoder_kernels.py) ------
  * Every hook below checks every size and index on the host (-1 without a
  * launch), keeps each device output between two guard bands of sentinel words

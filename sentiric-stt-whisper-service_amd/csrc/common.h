@@ -47,6 +47,12 @@ int ggml_ftype_of(int type);
 // one row of K (multiple of 32) values -> MX-fp8 codes q[K] + E8M0 scales s[K/32]
 void mx_quantize_row(const float* x, int K, uint8_t* q, uint8_t* s);
 float mx_dequant(uint8_t code, uint8_t s);  // e4m3fn code x 2^(s - 127)
+// engine.cpp: codes q [rows][K] and scales s [rows][K/32] as the fragment tiles
+// of an MX-fp8 decode weight (kernels.h DecW): qp = ceil16(rows) K code bytes
+// in pack_index order, sp = ceil16(rows) K/32 scale bytes, pad rows +0 x 2^0.
+// The one packer of the model loader and of mwx_test_gemm_dec_ex.
+void mx_pack_dec_weight(const uint8_t* q, const uint8_t* s, int64_t rows, int64_t K,
+                        std::vector<uint8_t>& qp, std::vector<uint8_t>& sp);
 
 // The 11 int32 header fields of a whisper ggml .bin file, in file order
 // (whisper.cpp whisper_model_load; upstream converter convert-pt-to-ggml.py).

@@ -3254,86 +3254,12 @@ extern "C" int mwx_test_dec_attn(struct mwx_context* ctx, int bf16, int grouped,
   }
 }
 
-// The decode GEMMs on given data (mwx_test_gemm_dec). The output lies between
-// two guard bands of sentinel words and starts as sentinel words itself, so a
-// store outside [M][N] (or one left out) shows.
+// The decode GEMMs on given data (mwx_test_gemm_dec / _gemm_dec_ex). Every
+// device output lies between two guard bands of sentinel words and starts as
+// sentinel words itself, so a store outside it (or one left out) shows.
 constexpr uint32_t TEST_GUARD_WORD = 0x7fc5a5a5u;  // a NaN no kernel produces
 constexpr size_t TEST_GUARD_WORDS = 1024;
 
-template <typename T>
-static int test_gemm_dec_impl(int mode, int M, int N, int K, const float* a, const float* w,
-                              const float* bias, const float* res, int* ks_out, float* out) {
-  const bool bf = std::is_same<T, __bf16>::value;
-  auto cvt = [&](float f) { return bf ? mwx::f32_to_bf16(f) : mwx::f32_to_f16(f); };
-  const size_t M64 = (size_t)(M + 63) / 64 * 64, N16 = (size_t)(N + 15) / 16 * 16;
-  std::vector<uint16_t> ap(M64 * K, 0), wp(N16 * K, 0);
-  for (int m = 0; m < M; ++m)
-    for (int k = 0; k < K; ++k) ap[mwx::pack_index(m, k, K)] = cvt(a[(size_t)m * K + k]);
-  for (int n = 0; n < N; ++n)
-    for (int k = 0; k < K; ++k) wp[mwx::pack_index(n, k, K)] = cvt(w[(size_t)n * K + k]);
-  const int ks_want = mode == 0 ? mwx::splitk_factor(K) : 1;
-  if (ks_want < 1 || ks_want > 8) return -4;
-  const size_t body = (size_t)ks_want * M * N, G = TEST_GUARD_WORDS, total = body + 2 * G;
-  std::vector<uint32_t> host(total, TEST_GUARD_WORD);
-  DevScratch m;
-  void* da = m.get(ap.size() * 2);
-  void* dw = m.get(wp.size() * 2);
-  void* dc = m.get(total * 4);
-  void* db = bias ? m.get((size_t)N * 4) : nullptr;
-  void* dr = res ? m.get((size_t)M * N * 4) : nullptr;
-  HIPC(hipMemcpy(da, ap.data(), ap.size() * 2, hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(dw, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(dc, host.data(), total * 4, hipMemcpyHostToDevice));
-  if (db) HIPC(hipMemcpy(db, bias, (size_t)N * 4, hipMemcpyHostToDevice));
-  if (dr) HIPC(hipMemcpy(dr, res, (size_t)M * N * 4, hipMemcpyHostToDevice));
-  float* c = (float*)dc + G;
-  const mwx::DecW<T> W((const T*)dw);
-  int ks = 1;
-  bool ok = true;
-  if (mode == 0) {
-    ks = mwx::gemm_splitk_partials<T>((const T*)da, W, M, N, K, c, nullptr);
-    ok = ks == ks_want;
-  } else {
-    mwx::EpiParams e;
-    e.c32 = c;
-    e.ldc = N;
-    if (mode == 2) {
-      e.bias = (const float*)db;
-      e.r32 = (const float*)dr;
-    }
-    ok = mwx::gemm_decode<T>(mode == 2 ? mwx::EPI_RES : mwx::EPI_F32, (const T*)da, W, M, N, K, e,
-                             nullptr);
-  }
-  HIPC(hipGetLastError());
-  HIPC(hipDeviceSynchronize());
-  if (!ok) return -4;
-  HIPC(hipMemcpy(host.data(), dc, total * 4, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < G; ++i)
-    if (host[i] != TEST_GUARD_WORD || host[G + body + i] != TEST_GUARD_WORD) return -3;
-  memcpy(out, host.data() + G, body * 4);
-  if (ks_out) *ks_out = ks;
-  return 0;
-}
-
-extern "C" int mwx_test_gemm_dec(struct mwx_context* ctx, int bf16, int mode, int M, int N, int K,
-                                 const float* a, const float* w, const float* bias,
-                                 const float* res, int* ks_out, float* out) {
-  if (!ctx || !a || !w || !out || mode < 0 || mode > 2) return -1;
-  if (M < 1 || M > 512 || N < 1 || N > 4096 || K < 32 || K > 8192 || K % 32) return -1;
-  if (mode == 2 && !res) return -1;
-  if (mode != 2 && (bias || res)) return -1;
-  try {
-    HIPC(hipSetDevice(ctx->c.device));
-    if (bf16) return test_gemm_dec_impl<__bf16>(mode, M, N, K, a, w, bias, res, ks_out, out);
-    return test_gemm_dec_impl<_Float16>(mode, M, N, K, a, w, bias, res, ks_out, out);
-  } catch (...) {
-    return -2;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Encoder kernels on given data (mwx_test_enc_attn / _gemm_enc / _layer_norm)
-// ---------------------------------------------------------------------------
 // A device output of `bytes` bytes between two guard bands of TEST_GUARD_WORD
 // (the slack up to the next 16 bytes belongs to the upper band). The body
 // starts as `init` (in-and-out buffers) or as all-ones bits: NaN as f16, bf16
@@ -3366,6 +3292,158 @@ struct GuardedBuf {
   }
 };
 
+template <typename T>
+static int test_gemm_dec_impl(const mwx_test_gemm_dec_args& g) {
+  const bool bf = std::is_same<T, __bf16>::value;
+  auto cvt = [&](float f) { return bf ? mwx::f32_to_bf16(f) : mwx::f32_to_f16(f); };
+  const int M = g.M, N = g.N, K = g.K, mode = g.mode;
+  const size_t M64 = (size_t)(M + 63) / 64 * 64, N16 = (size_t)(N + 15) / 16 * 16;
+  const int ks_want = mode == 0 ? mwx::splitk_factor(K) : 1;
+  if (ks_want < 1 || ks_want > 8) return -4;
+  DevScratch m;
+  auto up = [&](const void* src, size_t bytes) -> void* {
+    if (!src) return nullptr;
+    void* d = m.get(bytes);
+    HIPC(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+    return d;
+  };
+  const T* da = nullptr;
+  if (!g.ln) {
+    std::vector<uint16_t> ap(M64 * K, 0);
+    for (int r = 0; r < M; ++r)
+      for (int k = 0; k < K; ++k) ap[mwx::pack_index(r, k, K)] = cvt(g.a[(size_t)r * K + k]);
+    da = (const T*)up(ap.data(), ap.size() * 2);
+  }
+  mwx::DecW<T> W;
+  if (g.w8) {
+    std::vector<uint8_t> qp, sp;
+    mwx::mx_pack_dec_weight(g.wq, g.ws, N, K, qp, sp);
+    const uint8_t* dq = (const uint8_t*)up(qp.data(), qp.size());
+    W = mwx::DecW<T>(dq, (const uint8_t*)up(sp.data(), sp.size()));
+  } else {
+    std::vector<uint16_t> wp(N16 * K, 0);
+    for (int n = 0; n < N; ++n)
+      for (int k = 0; k < K; ++k) wp[mwx::pack_index(n, k, K)] = cvt(g.w[(size_t)n * K + k]);
+    W = mwx::DecW<T>((const T*)up(wp.data(), wp.size() * 2));
+  }
+  // the output: f32 [ks][M][N] of sentinel words, or (mode 3) 0xFFFF T words
+  const bool packed = mode == 3;
+  const size_t body = packed ? M64 * N * 2 : (size_t)ks_want * M * N * 4;
+  const std::vector<uint32_t> sent(std::max(body / 4, (size_t)K), TEST_GUARD_WORD);
+  GuardedBuf og, xog, xig;
+  void* dc = og.make(m, body, packed ? nullptr : sent.data());
+  mwx::LnFuse f;
+  if (g.ln) {
+    const size_t kb = (size_t)K * 4;
+    f.x_in = (const float*)xig.make(m, kb, g.x_in);
+    f.x_out = (float*)xog.make(m, kb, sent.data());
+    f.KS = g.KS;
+    f.pstride = K;
+    if (g.KS > 0) {
+      f.P = (const float*)up(g.P, (size_t)g.KS * kb);
+      f.pbias = (const float*)up(g.pbias, kb);
+    }
+    f.w = (const float*)up(g.ln_w, kb);
+    f.b = (const float*)up(g.ln_b, kb);
+    f.active = (const int*)up(g.active, 4);
+  }
+  int ks = 1;
+  bool ok = true;
+  if (mode == 0) {
+    ks = g.ln ? mwx::gemm_splitk_ln<T>(f, W, N, K, (float*)dc, nullptr)
+              : mwx::gemm_splitk_partials<T>(da, W, M, N, K, (float*)dc, nullptr);
+    ok = ks == ks_want;
+  } else {
+    mwx::EpiParams e;
+    e.ldc = N;
+    if (packed) {
+      e.c16 = dc;
+      e.pack_out = true;
+    } else {
+      e.c32 = (float*)dc;
+    }
+    if (mode >= 2) e.bias = (const float*)up(g.bias, (size_t)N * 4);
+    if (mode == 2) e.r32 = (const float*)up(g.res, (size_t)M * N * 4);
+    const int epi = mode == 1 ? mwx::EPI_F32 : mode == 2 ? mwx::EPI_RES : mwx::EPI_GELU;
+    ok = g.ln ? mwx::gemm_decode_ln<T>(epi, f, W, N, K, e, nullptr)
+              : mwx::gemm_decode<T>(epi, da, W, M, N, K, e, nullptr);
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  if (!ok) return -4;
+  bool clean = true;
+  if (packed) {
+    clean = og.take(g.out16);
+    if (clean)
+      for (int r = 0; r < M; ++r)
+        for (int n = 0; n < N; ++n) {
+          const uint16_t v = g.out16[mwx::pack_index(r, n, N)];
+          g.out[(size_t)r * N + n] = bf ? mwx::bf16_to_f32(v) : mwx::f16_to_f32(v);
+        }
+  } else {
+    clean = og.take(g.out);
+  }
+  if (g.ln) {
+    clean = xog.take(g.x_out) && clean;
+    clean = xig.take(g.x_in) && clean;
+  }
+  if (!clean) return -3;
+  if (g.ks_out) *g.ks_out = ks;
+  return 0;
+}
+
+extern "C" int mwx_test_gemm_dec_ex(struct mwx_context* ctx,
+                                    const struct mwx_test_gemm_dec_args* gp) {
+  if (!ctx || !gp) return -1;
+  const mwx_test_gemm_dec_args& g = *gp;
+  if (!g.out || g.mode < 0 || g.mode > 3) return -1;
+  if (g.M < 1 || g.M > 512 || g.N < 1 || g.N > 4096 || g.K < 32 || g.K > 8192 || g.K % 32)
+    return -1;
+  if (g.w8 ? (!g.wq || !g.ws) : !g.w) return -1;
+  if (g.mode == 2 && !g.res) return -1;
+  if (g.mode != 2 && g.res) return -1;
+  if (g.mode < 2 && g.bias) return -1;
+  // pack_index tiles of the output are 32 deep
+  if (g.mode == 3 && (!g.bias || !g.out16 || g.N % 32)) return -1;
+  if (g.ln) {
+    if (g.M != 1 || (g.mode != 0 && g.mode != 3)) return -1;
+    if (!g.x_in || !g.x_out || !g.ln_w || !g.ln_b || !g.active) return -1;
+    if (g.KS < 0 || g.KS > 8 || (g.KS > 0 && (!g.P || !g.pbias))) return -1;
+  } else if (!g.a) {
+    return -1;
+  }
+  // (the engine enables MX decode weights for bf16 models only)
+  if (g.w8 && !g.bf16) return -4;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    return g.bf16 ? test_gemm_dec_impl<__bf16>(g) : test_gemm_dec_impl<_Float16>(g);
+  } catch (...) {
+    return -2;
+  }
+}
+
+extern "C" int mwx_test_gemm_dec(struct mwx_context* ctx, int bf16, int mode, int M, int N, int K,
+                                 const float* a, const float* w, const float* bias,
+                                 const float* res, int* ks_out, float* out) {
+  if (mode < 0 || mode > 2) return -1;
+  mwx_test_gemm_dec_args g{};
+  g.bf16 = bf16;
+  g.mode = mode;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.a = a;
+  g.w = w;
+  g.bias = bias;
+  g.res = res;
+  g.ks_out = ks_out;
+  g.out = out;
+  return mwx_test_gemm_dec_ex(ctx, &g);
+}
+
+// ---------------------------------------------------------------------------
+// Encoder kernels on given data (mwx_test_enc_attn / _gemm_enc / _layer_norm)
+// ---------------------------------------------------------------------------
 template <typename T>
 static int test_enc_attn_impl(int B, int H, int L, const int* lens, float scale,
                               const uint16_t* q, const uint16_t* k, const uint16_t* vt, float* o) {

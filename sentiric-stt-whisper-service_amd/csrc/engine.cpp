@@ -541,6 +541,23 @@ struct Arena {
 };
 }  // namespace
 
+// The MX-fp8 decode weight as the W8 decode GEMMs read it (common.h; the model
+// loader and mwx_test_gemm_dec_ex both pack through here): the code of
+// (n, k) at pack_index(n, k, K), the scale of (n, 32-deep k-step kt) at
+// ((n >> 4) * K/32 + kt) * 16 + (n & 15); the rows up to the next multiple of
+// 16 hold code 0 under scale 127 (+0 x 2^0).
+void mx_pack_dec_weight(const uint8_t* q, const uint8_t* s, int64_t rows, int64_t K,
+                        std::vector<uint8_t>& qp, std::vector<uint8_t>& sp) {
+  const int64_t np = (rows + 15) / 16 * 16, KT = K / 32;
+  qp.assign((size_t)np * K, 0);
+  sp.assign((size_t)(np / 16) * KT * 16, 127);
+  for (int64_t n = 0; n < rows; ++n) {
+    for (int64_t k = 0; k < K; ++k) qp[pack_index(n, k, K)] = q[(size_t)n * K + k];
+    for (int64_t kt = 0; kt < KT; ++kt)
+      sp[((n >> 4) * KT + kt) * 16 + (n & 15)] = s[(size_t)n * KT + kt];
+  }
+}
+
 static bool upload_model(Context& C, const ModelFile& mf) {
   const Hparams& hp = C.hp;
   const int d = hp.n_audio_state, dt = hp.n_text_state;
@@ -657,19 +674,19 @@ static bool upload_model(Context& C, const ModelFile& mf) {
       return;
     }
     const int64_t KT = K / 32;
-    std::vector<uint8_t> q((size_t)np * K, 0), sc((size_t)(np / 16) * KT * 16, 127);
+    std::vector<uint8_t> rq((size_t)rows * K), rs((size_t)rows * KT), q, sc;
     std::vector<float> row(K);
-    std::vector<uint8_t> rq(K), rs(KT);
     if (rounded) rounded->assign(w.size(), 0);
     for (int64_t n = 0; n < rows; ++n) {
+      uint8_t* qn = rq.data() + (size_t)n * K;
+      uint8_t* sn = rs.data() + (size_t)n * KT;
       for (int64_t k = 0; k < K; ++k) row[k] = bf16_to_f32(w[(size_t)n * K + k]);
-      mx_quantize_row(row.data(), (int)K, rq.data(), rs.data());
-      for (int64_t k = 0; k < K; ++k) q[pack_index(n, k, K)] = rq[k];
-      for (int64_t kt = 0; kt < KT; ++kt) sc[((n >> 4) * KT + kt) * 16 + (n & 15)] = rs[kt];
+      mx_quantize_row(row.data(), (int)K, qn, sn);
       if (rounded)
         for (int64_t k = 0; k < K; ++k)
-          (*rounded)[(size_t)n * K + k] = f32_to_bf16(mx_dequant(rq[k], rs[k / 32]));
+          (*rounded)[(size_t)n * K + k] = f32_to_bf16(mx_dequant(qn[k], sn[k / 32]));
     }
+    mx_pack_dec_weight(rq.data(), rs.data(), rows, K, q, sc);
     A.add(q.data(), q.size(), (const void**)&slot->q);
     A.add(sc.data(), sc.size(), (const void**)&slot->s);
   };

@@ -804,6 +804,13 @@ extern "C" int mwx_test_dequantize(int type, const void* src, long n, float* dst
   return 0;
 }
 
+extern "C" int mwx_test_mx_quantize_rows(const float* x, int rows, int K, uint8_t* q, uint8_t* s) {
+  if (!x || !q || !s || rows < 0 || K < 32 || K % 32) return -1;
+  for (int r = 0; r < rows; ++r)
+    mwx::mx_quantize_row(x + (size_t)r * K, K, q + (size_t)r * K, s + (size_t)r * (K / 32));
+  return 0;
+}
+
 extern "C" void mwx_log_set(mwx_log_callback cb, void* user_data) {
   mwx::g_log_cb = cb;
   mwx::g_log_user = user_data;

@@ -159,6 +159,19 @@ class TestGemmEncArgs(C.Structure):
                 [(n, C.POINTER(C.c_uint8)) for n in ("k8", "v8", "ks8", "vs8")])
 
 
+class TestGemmDecArgs(C.Structure):
+    """mwx_test_gemm_dec_args (include/mwx_test.h)."""
+    __test__ = False
+    _fields_ = ([(n, C.c_int) for n in ("bf16", "mode", "w8", "ln", "M", "N", "K", "KS")] +
+                [(n, C.POINTER(C.c_float)) for n in ("a", "w")] +
+                [(n, C.POINTER(C.c_uint8)) for n in ("wq", "ws")] +
+                [(n, C.POINTER(C.c_float)) for n in ("bias", "res", "x_in", "P", "pbias", "ln_w",
+                                                     "ln_b")] +
+                [("active", C.POINTER(C.c_int)), ("x_out", C.POINTER(C.c_float)),
+                 ("ks_out", C.POINTER(C.c_int)), ("out", C.POINTER(C.c_float)),
+                 ("out16", C.POINTER(C.c_uint16))])
+
+
 class TestLogitsConst(C.Structure):
     """mwx_test_logits_const (include/mwx_test.h): the kernels' LogitsConst."""
     __test__ = False
@@ -620,6 +633,22 @@ def dequantize(qtype: int, raw: bytes, n: int) -> np.ndarray:
     if rc != 0:
         raise ValueError(f"mwx_test_dequantize({qtype}, n={n}) returned {rc}")
     return out
+
+
+def mx_quantize_rows(x: np.ndarray):
+    """mwx_test_mx_quantize_rows: the load-time MX-fp8 quantizer (host only).
+    x [rows][K] f32 -> (e4m3fn codes uint8 [rows][K], E8M0 scales [rows][K/32])."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    rows, K = x.shape
+    q = np.empty((rows, K), np.uint8)
+    s = np.empty((rows, K // 32), np.uint8)
+    fn = lib().mwx_test_mx_quantize_rows
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    rc = fn(x.ctypes.data_as(C.POINTER(C.c_float)), rows, K, q.ctypes.data, s.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"mwx_test_mx_quantize_rows(rows={rows}, K={K}) returned {rc}")
+    return q, s
 
 
 def quantize_model(in_path: str, out_path: str, qtype: int) -> None:
@@ -1407,6 +1436,63 @@ class Context:
         if rc != 0:
             raise RuntimeError(f"mwx_test_gemm_dec failed ({rc})")
         return out[:ks.value].copy() if mode == 0 else out[0]
+
+    def test_gemm_dec_ex(self, a=None, w=None, *, bf16: bool, mode: int, wq=None, ws=None,
+                         bias=None, res=None, ln=None):
+        """mwx_test_gemm_dec_ex (include/mwx_test.h). a [M][K] f32; the weights
+        as w [N][K] f32 or as MX-fp8 codes wq [N][K] and scales ws [N][K/32]
+        (uint8; either selects w8). ln: a dict x_in [K], w, b [K], active
+        (0 / 1), P [KS][K] and pbias [K] (or neither): the folded LayerNorm
+        as the A operand (M = 1). Returns the slabs [KS][M][N] (mode 0), c
+        [M][N] (modes 1, 2) or (c [M][N], the packed buffer's uint16 words
+        [ceil64(M)][N] flat) (mode 3); with ln, a tuple of that, x_out (the
+        uint32 words of the residual buffer) and x_in as read back."""
+        f32 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float32)
+        u8 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.uint8)
+        a, w, bias, res, wq, ws = f32(a), f32(w), f32(bias), f32(res), u8(wq), u8(ws)
+        g = TestGemmDecArgs()
+        g.bf16, g.mode = int(bf16), mode
+        g.w8 = int(wq is not None or ws is not None)
+        g.ln = int(ln is not None)
+        x_in = x_out = None
+        keep = []
+        ptr = lambda x, t: C.POINTER(t)() if x is None else x.ctypes.data_as(C.POINTER(t))
+        if ln is not None:
+            x_in = np.array(ln["x_in"], dtype=np.float32, order="C")
+            K = x_in.shape[0]
+            x_out = np.empty(K, np.uint32)
+            P, pbias = f32(ln.get("P")), f32(ln.get("pbias"))
+            lw, lb = f32(ln["w"]), f32(ln["b"])
+            act = np.asarray([ln.get("active", 1)], np.int32)
+            assert x_in.shape == lw.shape == lb.shape == (K,)
+            g.KS = 0 if P is None else P.shape[0]
+            assert P is None or P.shape == (g.KS, K)
+            assert pbias is None or pbias.shape == (K,)
+            keep += [P, pbias, lw, lb, act]
+            g.x_in, g.x_out = ptr(x_in, C.c_float), ptr(x_out.view(np.float32), C.c_float)
+            g.P, g.pbias = ptr(P, C.c_float), ptr(pbias, C.c_float)
+            g.ln_w, g.ln_b, g.active = ptr(lw, C.c_float), ptr(lb, C.c_float), ptr(act, C.c_int)
+        M = 1 if a is None else a.shape[0]
+        N = next(x.shape[0] for x in (w, wq, ws, bias) if x is not None)
+        K = next(x.shape[-1] for x in (a, x_in, w, wq) if x is not None)
+        for x in (w, wq):
+            assert x is None or x.shape == (N, K), x.shape
+        assert ws is None or ws.shape == (N, K // 32), ws.shape
+        assert bias is None or bias.shape == (N,)
+        assert res is None or res.shape == (M, N)
+        g.M, g.N, g.K = M, N, K
+        g.a, g.w, g.bias, g.res = (ptr(x, C.c_float) for x in (a, w, bias, res))
+        g.wq, g.ws = ptr(wq, C.c_uint8), ptr(ws, C.c_uint8)
+        out = np.empty((8 if mode == 0 else 1, M, N), np.float32)
+        out16 = np.empty((M + 63) // 64 * 64 * N, np.uint16) if mode == 3 else None
+        ks = C.c_int(0)
+        g.ks_out, g.out, g.out16 = C.pointer(ks), ptr(out, C.c_float), ptr(out16, C.c_uint16)
+        fn = lib().mwx_test_gemm_dec_ex
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(TestGemmDecArgs)]
+        self._hook_rc("mwx_test_gemm_dec_ex", fn(self.ctx, C.byref(g)))
+        got = out[:ks.value].copy() if mode == 0 else (out[0], out16) if mode == 3 else out[0]
+        return got if ln is None else (got, x_out, x_in)
 
     @staticmethod
     def _hook_rc(name: str, rc: int):

@@ -29,6 +29,15 @@ GEMM: float64 product of the T-rounded operands; per element
   bound = Kn 2^-24 sum_k |a_mk| |w_nk| + 2^-24 |ref|
 (Kn = the number of k summed: products of two 16-bit values are exact in f32,
 each of the at most Kn f32 additions rounds once, in any order).
+
+MX-fp8 weights (W8 kernels): the e4m3 codes of a lane's 8 k are widened to bf16
+under the E8M0 scale of (column, k / 32), exactly, and the bf16 chain runs
+unchanged: the reference is gemm_ref on mx_decode(codes, scales), the same
+bound, and the kernel's bits are those of the 16-bit kernel on those values
+(w8_widen restates the addressing, with deliberately broken variants).
+The FFN1 epilogue stores T(gelu_ggml(acc + bias)) at pack_index(m, n, N) of a
+buffer of ceil64(M) rows (pack_store / packed_store_ok). splitk_factor,
+skinny_split and ln_fold_serves restate the launchers' K rules.
 """
 import numpy as np
 
@@ -227,3 +236,157 @@ def gemm_emulate(a, w, bf16, k0=0, k1=None):
     w32 = round_t(w, bf16)[:, k0:k1]
     prod = a32[:, None, :] * w32[None, :, :]
     return np.cumsum(prod, axis=2, dtype=np.float32)[:, :, -1]
+
+
+# ------------------------------------------------- the kernels' K splits
+
+def splitk_factor(K):
+    """k_gemm.hip splitk_factor: the largest KS <= 8 whose slices are four
+    waves of 1 .. 5 32-deep k-steps; 0: K not served by the split-K kernels."""
+    if K % 128:
+        return 0
+    S = K // 32
+    for ks in range(8, 0, -1):
+        if S % ks == 0 and (S // ks) % 4 == 0 and S // ks // 4 <= 5:
+            return ks
+    return 0
+
+
+def skinny_split(K):
+    """k_gemm.hip skinny_split: (waves, k-steps per wave) of the full-K
+    kernels, the most waves <= 16 with 1 / 2 / 3 / 4 / 6 / 8 / 10 k-steps
+    each; None: K not served."""
+    if K % 32:
+        return None
+    S = K // 32
+    for w in range(16, 0, -1):
+        if S % w == 0 and S // w in (1, 2, 3, 4, 6, 8, 10):
+            return w, S // w
+    return None
+
+
+def ln_fold_serves(K, mode):
+    """Whether gemm_splitk_ln (mode 0) / gemm_decode_ln (mode 3) take the
+    width: the row in 2048 elements of LDS, and the K split above (the full-K
+    kernel's prologue needs four waves)."""
+    if K > 2048 or K % 8:
+        return False
+    if mode == 0:
+        return splitk_factor(K) > 0
+    s = skinny_split(K)
+    return s is not None and s[0] >= 4
+
+
+# ------------------------------------------------------- fragment tiles
+
+def pack_index(n, k, K):
+    """kernels.h pack_index: element (n, k) of a [rows][K] operand in fragment
+    tiles: 16-row strip nt, 32-deep k-step kt, lane (k % 32 / 8) 16 + n % 16,
+    8 consecutive k per lane."""
+    n, k = np.asarray(n, np.int64), np.asarray(k, np.int64)
+    return (((n >> 4) * (K >> 5) + (k >> 5)) * 64 + ((k & 31) >> 3) * 16 + (n & 15)) * 8 + (k & 7)
+
+
+SENT16 = np.uint16(0xFFFF)  # the packed output buffer's words before the launch
+
+
+def pack_store(vals, broken=None):
+    """The packed store of the decode FFN1 epilogue on a 16-bit [M][N] array:
+    the buffer of ceil64(M) N words it leaves. broken 'transposed': the store
+    at pack_index(n, m, N) (stores past the buffer dropped); 'drop64': rows
+    >= 64 not stored."""
+    vals = np.asarray(vals, np.uint16)
+    M, N = vals.shape
+    buf = np.full((M + 63) // 64 * 64 * N, SENT16)
+    m, n = np.meshgrid(np.arange(M), np.arange(N), indexing="ij")
+    idx = pack_index(n, m, N) if broken == "transposed" else pack_index(m, n, N)
+    keep = idx < buf.size
+    if broken == "drop64":
+        keep &= m < 64
+    buf[idx[keep]] = vals[keep]
+    return buf
+
+
+def packed_rows(buf, M, N):
+    """The packed buffer as [ceil64(M)][N] words in (row, column) order."""
+    M64 = (M + 63) // 64 * 64
+    m, n = np.meshgrid(np.arange(M64), np.arange(N), indexing="ij")
+    return np.asarray(buf, np.uint16)[pack_index(m, n, N)]
+
+
+def packed_store_ok(buf, M, N):
+    """Every word of rows < M written, every word of the pad rows M ..
+    ceil64(M) - 1 still the sentinel. Returns (ok, rows [M][N])."""
+    assert np.size(buf) == (M + 63) // 64 * 64 * N
+    rows = packed_rows(buf, M, N)
+    return bool((rows[:M] != SENT16).all() and (rows[M:] == SENT16).all()), rows[:M]
+
+
+# ------------------------------------------------ MX-fp8 decode weights
+
+FINITE_CODES = np.asarray([c for c in range(256) if c & 0x7F != 0x7F], np.uint8)  # e4m3fn: 254
+
+
+def mx_decode(codes, scales):
+    """encoder_ref.mx_decode (that module imports this one): e4m3fn codes
+    [N][K] under E8M0 scales [N][K/32], code x 2^(s - 127), exact in f32."""
+    from encoder_ref import mx_decode as decode
+    return decode(codes, scales)
+
+
+def mx_dec_weights(seed, N, K, span=(-30, 8)):
+    """codes [N][K] drawn from the finite e4m3fn codes and scales [N][K/32]
+    with the block exponents s - 127 uniform over span (both ends included):
+    neighbouring blocks differ by many binades, so a scale taken from the
+    wrong block is no rounding error."""
+    rng = np.random.default_rng([seed, N, K, span[0] + 1000, span[1] + 1000])
+    codes = FINITE_CODES[rng.integers(0, len(FINITE_CODES), (N, K))]
+    scales = (127 + rng.integers(span[0], span[1] + 1, (N, K // 32))).astype(np.uint8)
+    return codes, scales
+
+
+def mx_probe_weights(seed, N, K, span=(-100, 100)):
+    """The identity probe's weights: every finite code and every exponent of
+    span that N K / 32 blocks can hold (evenly spread, both ends included),
+    each as often as the other, in a seeded shuffle."""
+    rng = np.random.default_rng([seed, N, K])
+    codes = np.resize(FINITE_CODES, N * K)
+    nb = N * K // 32
+    exps = np.round(np.linspace(span[0], span[1], min(nb, span[1] - span[0] + 1))).astype(np.int64)
+    scales = np.resize(127 + exps, nb).astype(np.uint8)
+    return rng.permutation(codes).reshape(N, K), rng.permutation(scales).reshape(N, K // 32)
+
+
+W8_BROKEN = ("scale_kt+1", "scale_n^1", "scale_per_64", "codes_reversed", "halves_swapped")
+
+
+def w8_widen(codes, scales, broken=None):
+    """What the W8 kernels feed the MFMA for element (n, k): the lane holding
+    k % 32 / 8 of column n widens its 8 codes under the scale word of (n,
+    k / 32). broken: 'scale_kt+1' the scale of the next k-step (the last of a
+    row wraps to its first), 'scale_n^1' of the neighbouring column,
+    'scale_per_64' of the even k-step of each pair, 'codes_reversed' a lane's
+    8 codes in reverse order, 'halves_swapped' the two halves of a lane's
+    first 4-byte word swapped."""
+    codes, scales = np.asarray(codes, np.uint8), np.asarray(scales, np.uint8)
+    N, K = codes.shape
+    n, kt, k = np.arange(N)[:, None], np.arange(K // 32)[None], np.arange(K)
+    if broken == "scale_kt+1":
+        scales = scales[n, (kt + 1) % (K // 32)]
+    elif broken == "scale_n^1":
+        scales = scales[np.minimum(n ^ 1, N - 1), kt]
+    elif broken == "scale_per_64":
+        scales = scales[n, kt & ~1]
+    elif broken == "codes_reversed":
+        codes = codes[:, k ^ 7]
+    elif broken == "halves_swapped":
+        codes = codes[:, np.where(k & 4, k, k ^ 2)]
+    else:
+        assert broken is None, broken
+    return mx_decode(codes, scales)
+
+
+def w8_emulate(a, codes, scales, k0=0, k1=None, broken=None):
+    """The W8 path in f32: the codes widened to bf16 exactly, then the 16-bit
+    chain (gemm_emulate) on bf16 activations."""
+    return gemm_emulate(a, w8_widen(codes, scales, broken), True, k0, k1)

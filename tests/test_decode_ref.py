@@ -91,3 +91,76 @@ def test_gemm_emulation_within_bound(bf16):
         assert np.max(np.abs(ref2 - ref) / bound) > 10.0
     print(f"gemm, {'bf16' if bf16 else 'f16'}: worst emulation ratio {worst:.3f}")
     assert worst <= 1.0
+
+
+# ------------------------------------------- the rest of the GEMM family
+
+FULL_KS = (96, 384, 768, 1280, 1536, 2048, 3072, 4096, 5120)  # test_gemm_decode_full_k
+MODEL_WIDTHS = (384, 512, 768, 1024, 1280)
+
+
+def test_k_split_rules_restate_the_launchers():
+    """splitk_factor / skinny_split as the GPU tests restate them: the
+    factors the existing split-K test records, every k-steps-per-wave case of
+    the full-K set, and every model width served by both LayerNorm folds."""
+    assert {K: dr.splitk_factor(K) for K in dr.SPLITK_KS} == dr.SPLITK_KS
+    assert [dr.splitk_factor(K) for K in (96, 160, 6144 + 128)] == [0, 0, 0]
+    assert sorted({dr.skinny_split(K)[1] for K in FULL_KS}) == [1, 2, 3, 4, 6, 8, 10]
+    assert dr.skinny_split(48) is None and dr.skinny_split(32 * 17) is None
+    for K in MODEL_WIDTHS + (2048,):
+        assert dr.ln_fold_serves(K, 0) and dr.ln_fold_serves(K, 3), K
+    assert not dr.ln_fold_serves(96, 0) and not dr.ln_fold_serves(96, 3)   # K % 128; 3 waves
+    assert not dr.ln_fold_serves(2048 + 128, 0) and not dr.ln_fold_serves(4096, 3)
+
+
+def test_probe_weights_cover_every_code_and_exponent():
+    for K, nexp in ((128, 104), (512, 201)):
+        codes, scales = dr.mx_probe_weights(0, 26, K)
+        assert set(codes.reshape(-1)) == set(dr.FINITE_CODES) and len(dr.FINITE_CODES) == 254
+        e = scales.astype(np.int64) - 127
+        assert e.min() == -100 and e.max() == 100 and len(set(e.reshape(-1))) == nexp
+        w = dr.mx_decode(codes, scales)
+        # every value a normal bf16 (or zero): the probe's products are exact
+        assert np.array_equal(dr.bf16_round(w), w)
+        assert (np.abs(w[w != 0]) >= 2.0 ** -126).all() and np.isfinite(w).all()
+
+
+@pytest.mark.parametrize("K", [128, 1280])
+def test_w8_emulation_within_bound_and_broken_variants_rejected(K):
+    """The W8 path (codes widened exactly, then the bf16 chain) holds gemm_ref's
+    bound on the dequantised weights; a scale from the next k-step, from the
+    neighbouring column or shared by 64 k, a lane's codes reversed and its
+    first word's halves swapped each exceed it, and each fails the identity
+    probe (A = I: the output is the widened weight itself)."""
+    M, N = 5, 26
+    codes, scales = dr.mx_dec_weights(0, N, K)
+    e = scales.astype(np.int64) - 127
+    assert e.min() == -30 and e.max() == 8
+    a, _ = dr.gemm_inputs(0, M, N, K)
+    ref, bound = dr.gemm_ref(a, dr.mx_decode(codes, scales), True)
+    good = dr.worst_ratio(dr.w8_emulate(a, codes, scales), ref, bound)
+    print(f"W8 K {K}: worst emulation ratio {good:.3f}")
+    assert good <= 1.0
+    pc, ps = dr.mx_probe_weights(0, N, min(K, 512))
+    want = dr.mx_decode(pc, ps)
+    assert np.array_equal(dr.w8_widen(pc, ps).view(np.uint32), want.view(np.uint32))
+    for broken in dr.W8_BROKEN:
+        r = dr.worst_ratio(dr.w8_emulate(a, codes, scales, broken=broken), ref, bound)
+        wrong = (dr.w8_widen(pc, ps, broken).view(np.uint32) != want.view(np.uint32)).mean()
+        print(f"W8 K {K} {broken}: ratio {r:.3g}, probe words wrong {wrong:.3f}")
+        assert r > 1.0 and wrong > 0.25, broken
+
+
+@pytest.mark.parametrize("N", [64, 96, 160])
+@pytest.mark.parametrize("M", [1, 5, 17, 64, 65, 100])
+def test_packed_store_check_rejects_broken_stores(M, N):
+    """The packed-store check (rows < M written, pad rows untouched, the
+    values at pack_index(m, n, N)) passes the store it restates and fails a
+    transposed index and, above 64 rows, a store that drops rows >= 64."""
+    vals = (np.arange(M * N, dtype=np.uint32) % 0xF000).astype(np.uint16).reshape(M, N)
+    ok, rows = dr.packed_store_ok(dr.pack_store(vals), M, N)
+    assert ok and np.array_equal(rows, vals)
+    ok, rows = dr.packed_store_ok(dr.pack_store(vals, "transposed"), M, N)
+    assert not (ok and np.array_equal(rows, vals))
+    ok, rows = dr.packed_store_ok(dr.pack_store(vals, "drop64"), M, N)
+    assert (ok and np.array_equal(rows, vals)) == (M <= 64)

@@ -2,11 +2,13 @@
 float64 references on chosen shapes (tests/decode_ref.py states the contract,
 the bound and the inputs; test_decode_ref.py checks the bound on the CPU).
 Every case runs the f16 and the bf16 instantiation through one f16 context
-(mwx_test_dec_attn / mwx_test_gemm_dec take the type as a flag)."""
+(mwx_test_dec_attn / mwx_test_gemm_dec / mwx_test_gemm_dec_ex take the type
+as a flag; the MX-fp8 weight kernels take their codes and scales directly)."""
 import numpy as np
 import pytest
 
 import decode_ref as dr
+import encoder_ref as er
 import mwx
 
 pytestmark = pytest.mark.gpu
@@ -270,6 +272,7 @@ def test_hooks_refuse_indices_outside_their_buffers(ctx):
 
 GEMM_N = (16, 26, 80)
 GEMM_M = (1, 5, 16, 17, 33, 64, 65, 100)
+FULL_KS = (96, 384, 768, 1280, 1536, 2048, 3072, 4096, 5120)  # every k-steps-per-wave case
 
 
 def both_shared(run):
@@ -311,7 +314,7 @@ def test_gemm_splitk_partials(ctx, bf16, K):
 
 
 @pytest.mark.parametrize("bf16", TYPES)
-@pytest.mark.parametrize("K", [96, 384, 768, 1280, 1536, 2048, 3072, 4096, 5120])
+@pytest.mark.parametrize("K", FULL_KS)
 def test_gemm_decode_full_k(ctx, bf16, K):
     """gemm_skinny at every k-steps-per-wave case of its K split (1, 2, 3, 4,
     6, 8, 10) and gemm_dec_shared above 64 rows, against float64."""
@@ -350,3 +353,278 @@ def test_gemm_decode_residual_epilogue(ctx, bf16):
             assert np.isfinite(c).all() and ratio.max() <= 1.0, (K, M, float(ratio.max()))
             worst = max(worst, float(ratio.max()))
     print(f"EPI_RES: worst ratio {worst:.3f}")
+
+
+# ------------------------------ MX-fp8 weights, FFN1 epilogue, LayerNorm fold
+# (mwx_test_gemm_dec_ex; the W8 kernels are bf16 only, as the engine runs them)
+
+PACK_N = (64, 96, 160)
+PACK_M = (1, 5, 17, 64, 65, 100)
+LN_KS = (96, 384, 512, 768, 1024, 1280, 2048)   # 96: served by neither fold
+MODEL_WIDTHS = (384, 512, 768, 1024, 1280)
+KINDS = [pytest.param((False, False), id="f16"), pytest.param((True, False), id="bf16"),
+         pytest.param((True, True), id="w8")]
+
+
+@pytest.fixture(scope="module")
+def gelu_tab(ctx):
+    return ctx.test_gelu_table()
+
+
+def same_bits(x, y):
+    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
+    return x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes()
+
+
+def run_rows(M, run):
+    """run() once; above 64 rows with the shared-A kernels and with the
+    per-strip grids, which must give the same bits (every output of run())."""
+    if M <= 64:
+        return run()
+    shared, strips = both_shared(run)
+    one = isinstance(shared, np.ndarray)
+    for x, y in zip((shared,) if one else shared, (strips,) if one else strips):
+        assert same_bits(x, y), "shared-A and per-strip kernels differ"
+    return shared
+
+
+def widen16(u16, bf16):
+    u16 = np.ascontiguousarray(u16, dtype=np.uint16)
+    if bf16:
+        return (u16.astype(np.uint32) << 16).view(np.float32)
+    return u16.view(np.float16).astype(np.float32)
+
+
+def weights(kind, seed, N, K, span=None):
+    """(keywords of the weight operand, the values the kernel multiplies by):
+    16-bit weights of std K^-1/2, or MX-fp8 codes and scales (span None: the
+    MX encoding of those weights; else block exponents uniform over span)."""
+    bf16, w8 = kind
+    if not w8:
+        w = dr.gemm_inputs(seed, 1, N, K)[1]
+        return dict(w=w), dr.round_t(w, bf16)
+    if span is None:
+        codes, scales = er.mx_encode(dr.bf16_round(dr.gemm_inputs(seed, 1, N, K)[1]))
+    else:
+        codes, scales = dr.mx_dec_weights(seed, N, K, span)
+    return dict(wq=codes, ws=scales), dr.mx_decode(codes, scales)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("K", [128, 512])
+def test_w8_identity_probe(ctx, K, mode):
+    """A = the K x K identity: output (k, n) (mode 0: of slab k // (K / KS)) is
+    the bf16 widening of code[n][k] under scale[n][k / 32], bit for bit, and
+    every other slab an exact 0: every (column, k) code position and every
+    scale word of the partial-strip N = 26, all 254 finite codes, exponents
+    -100 .. 100, through the per-strip and the shared-A kernels. (A code 0x00
+    or 0x80 gives a zero of either sign: a sum that starts at +0 has no -0.
+    Exponents whose products are bf16 subnormals or overflow are out of
+    scope: they are no weight scale the loader's quantizer emits for bf16
+    weights of a trained model, and bf16 MFMA inputs below 2^-126 are not
+    pinned by the contract.)"""
+    N, KS = 26, dr.SPLITK_KS[K] if mode == 0 else 1
+    codes, scales = dr.mx_probe_weights(0, N, K)
+    want = dr.mx_decode(codes, scales).T                       # [K][N]
+    got = run_rows(K, lambda: ctx.test_gemm_dec_ex(np.eye(K, dtype=np.float32), bf16=True,
+                                                   mode=mode, wq=codes, ws=scales))
+    got = got.reshape(KS, K, N)
+    exp = np.zeros((KS, K, N), np.float32)
+    for ks in range(KS):
+        rows = slice(ks * K // KS, (ks + 1) * K // KS)
+        exp[ks, rows] = want[rows]
+    nz = exp != 0
+    bad = (nz & (bits(got) != bits(exp))) | (~nz & (got != 0))
+    assert not bad.any(), (f"{int(bad.sum())} of {bad.size} words differ, first (slab, k, n) = "
+                           f"{tuple(np.argwhere(bad)[0])}")
+
+
+@pytest.fixture(scope="module")
+def w8_runs(ctx):
+    """(mode, K) -> the launches of the W8 kernels and of the bf16 16-bit
+    kernels on the dequantised weights, made once for both tests below."""
+    cache = {}
+
+    def get(mode, K):
+        if (mode, K) not in cache:
+            out = []
+            for N in (PACK_N if mode == 3 else GEMM_N):
+                codes, scales = dr.mx_dec_weights(mode, N, K)      # exponents -30 .. 8
+                w = dr.mx_decode(codes, scales)
+                # mode 3: a times a power of two (exact) that brings the
+                # pre-activations to a std of about 4, GELU's own range
+                rms = np.sqrt((w.astype(np.float64) ** 2).sum(axis=1).mean())
+                shrink = np.float32(2.0 ** -np.round(np.log2(rms / 4))) if mode == 3 else 1
+                for M in GEMM_M:
+                    a = dr.gemm_inputs(10 + mode, M, N, K)[0] * np.float32(shrink)
+                    rng = np.random.default_rng([K, M, N])
+                    bias = rng.standard_normal(N).astype(np.float32) if mode >= 2 else None
+                    if mode == 3:
+                        bias = np.linspace(-14.0, 14.0, N).astype(np.float32)
+                    res = rng.standard_normal((M, N)).astype(np.float32) if mode == 2 else None
+                    kw = dict(bf16=True, mode=mode, bias=bias, res=res)
+                    g8 = run_rows(M, lambda: ctx.test_gemm_dec_ex(a, wq=codes, ws=scales, **kw))
+                    g16 = run_rows(M, lambda: ctx.test_gemm_dec_ex(a, w, **kw))
+                    out.append(dict(M=M, N=N, a=a, w=w, bias=bias, res=res, g8=g8, g16=g16))
+            cache[mode, K] = out
+        return cache[mode, K]
+    return get
+
+
+W8_CASES = [(0, K) for K in sorted(dr.SPLITK_KS)] + [(m, K) for m in (1, 2, 3) for K in FULL_KS]
+
+
+@pytest.mark.parametrize("mode,K", W8_CASES)
+def test_w8_equals_16bit_kernel_on_dequantised_weights(w8_runs, mode, K):
+    """The contract above e8m0_to_f32: the codes are widened to bf16 exactly
+    and the 16-bit MFMA chain runs unchanged, so the W8 kernels give the bits
+    of the bf16 kernels on mx_decode(codes, scales): slabs, EPI_F32, EPI_RES
+    and the packed EPI_GELU buffer, per-strip and shared-A (all four equal)."""
+    for c in w8_runs(mode, K):
+        g8, g16 = (c["g8"], c["g16"]) if mode == 3 else ((c["g8"],), (c["g16"],))
+        for x, y in zip(g8, g16):
+            assert same_bits(x, y), (c["M"], c["N"])
+
+
+def gelu_packed_check(tab, got, a, w, bias, bf16):
+    """The packed FFN1 output (c [M][N], the raw buffer): rows < M written and
+    the pad rows untouched, the hook's unpacking = pack_index, every value a
+    gelu_ggml output of an f16 input within the accumulator bound. Returns the
+    float64 pre-activations."""
+    c, raw = got
+    M, N = c.shape
+    ok, rows = dr.packed_store_ok(raw, M, N)
+    assert ok, f"M {M} N {N}: a word of rows < M not written, or a pad row written"
+    assert same_bits(widen16(rows, bf16), c)
+    ref, beta = dr.gemm_ref(a, w, bf16)
+    x64, bx = er.add_bound(ref, beta, bias.astype(np.float64)[None])
+    okv = er.gelu_candidates_ok(c, x64, bx, tab, lambda g, sel: er.round_t(g, bf16))
+    assert okv.all(), (f"M {M} N {N}: {(~okv).sum()} outputs are no GELU value of an f16 input "
+                       f"within the bound, first at {np.argwhere(~okv)[0]}")
+    return x64
+
+
+@pytest.mark.parametrize("mode,K", W8_CASES)
+def test_w8_against_float64(w8_runs, gelu_tab, mode, K):
+    """The same launches against gemm_ref on the dequantised weights (exact in
+    float64; the W operand has no rounding), the 16-bit tests' bound."""
+    KS = dr.SPLITK_KS[K] if mode == 0 else 1
+    worst = 0.0
+    for c in w8_runs(mode, K):
+        M, N, a, w, got = c["M"], c["N"], c["a"], c["w"], c["g8"]
+        if mode == 3:
+            gelu_packed_check(gelu_tab, got, a, w, c["bias"], True)
+            continue
+        assert got.shape == ((KS, M, N) if mode == 0 else (M, N)) and np.isfinite(got).all()
+        for ks in range(KS):
+            ref, bound = dr.gemm_ref(a, w, True, ks * K // KS, (ks + 1) * K // KS)
+            want = ref
+            if mode == 2:
+                want = ref + c["bias"][None] + c["res"]
+                bound = bound + 2.0 ** -24 * (np.abs(ref + c["bias"][None]) + np.abs(want))
+            ratio = np.abs((got[ks] if mode == 0 else got) - want) / bound
+            assert ratio.max() <= 1.0, (M, N, ks, float(ratio.max()))
+            worst = max(worst, float(ratio.max()))
+    print(f"W8 mode {mode} K {K}: " + ("every packed output a GELU value within the bound"
+                                       if mode == 3 else
+                                       f"worst |got - ref| / bound = {worst:.3f}"))
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("K", [128, 1280])
+def test_gemm_decode_gelu_packed(ctx, gelu_tab, kind, K):
+    """The decode FFN1 epilogue (EPI_GELU, pack_out) of gemm_skinny and, above
+    64 rows, gemm_dec_shared (K 1280; equal bits): pre-activations spread over
+    [-14, 14] by the bias (both saturation branches and everything between;
+    over the case's launches at least 5 % beyond 10 and 5 % below 1), every
+    output a gelu_ggml value (tanhf path) of an f16 input within the bound,
+    stored at pack_index(m, n, N); rows M .. ceil64(M) - 1 keep the sentinel."""
+    bf16, w8 = kind
+    xs = []
+    for N in PACK_N:
+        kw, w = weights(kind, 20, N, K)
+        bias = np.linspace(-14.0, 14.0, N).astype(np.float32)
+        for M in PACK_M:
+            a, _ = dr.gemm_inputs(21, M, N, K)
+            got = run_rows(M, lambda: ctx.test_gemm_dec_ex(a, bf16=bf16, mode=3, bias=bias, **kw))
+            xs.append(np.abs(gelu_packed_check(gelu_tab, got, a, w, bias, bf16)).reshape(-1))
+    x = np.concatenate(xs)
+    assert (x > 10).mean() >= 0.05 and (x < 1).mean() >= 0.05, ((x > 10).mean(), (x < 1).mean())
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("K", LN_KS)
+def test_ln_fold_equals_two_launches(ctx, kind, K):
+    """gemm_splitk_ln (the slabs) and gemm_decode_ln (the packed GELU output, N
+    = 4 K capped at 4096) against layer_norm_dec followed by the plain GEMM, bit
+    for bit, after 0 / 1 / 5 / 8 producer slabs: the outputs, x_out = that
+    LayerNorm's residual, x_in unchanged, no guard band touched; an inactive
+    row's x_out is a copy of x_in. A width is refused exactly where
+    splitk_factor / skinny_split (with four waves) refuse it, and no model
+    width is."""
+    bf16, w8 = kind
+    rng = np.random.default_rng(K)
+    x = rng.standard_normal(K).astype(np.float32)
+    lw = (1.0 + 0.5 * rng.standard_normal(K)).astype(np.float32)
+    lb = (0.5 * rng.standard_normal(K)).astype(np.float32)
+    Pall = rng.standard_normal((8, K)).astype(np.float32)
+    pb = (0.3 * rng.standard_normal(K)).astype(np.float32)
+    for mode, N in ((0, 90), (3, min(4 * K, 4096))):
+        served = dr.ln_fold_serves(K, mode)
+        assert served or K not in MODEL_WIDTHS, f"the fold does not serve model width {K}"
+        kw, _ = weights(kind, 30, N, K, span=(-14, -10))
+        kw.update(bf16=bf16, mode=mode,
+                  bias=np.linspace(-14.0, 14.0, N).astype(np.float32) if mode == 3 else None)
+        for KS in (0, 1, 5, 8):
+            fuse = dict(x_in=x, w=lw, b=lb, active=1, P=Pall[:KS] if KS else None,
+                        pbias=pb if KS else None)
+            try:
+                fold, x_out, x_after = ctx.test_gemm_dec_ex(ln=fuse, **kw)
+            except NotImplementedError:
+                assert not served, f"K {K} mode {mode}: the fold was lost"
+                continue
+            assert served, f"K {K} mode {mode}: served against the launcher's rule"
+            y, x1 = ctx.test_layer_norm(x[None], lw, lb, bf16=bf16, dec=True,
+                                        P=Pall[:KS, None] if KS else None, pbias=fuse["pbias"])
+            two = ctx.test_gemm_dec_ex(y, **kw)
+            for f, t in zip(*((fold, two) if mode == 3 else ((fold,), (two,)))):
+                assert same_bits(f, t), (mode, KS)
+            if mode == 3:
+                assert dr.packed_store_ok(fold[1], 1, N)[0]
+            assert same_bits(x_out, bits(x1[0])), (mode, KS, "x_out is not the residual")
+            assert same_bits(bits(x_after), bits(x)), (mode, KS, "x_in changed")
+        if served:
+            fuse = dict(x_in=x, w=lw, b=lb, active=0, P=Pall[:5], pbias=pb)
+            _, x_out, x_after = ctx.test_gemm_dec_ex(ln=fuse, **kw)
+            assert same_bits(x_out, bits(x)) and same_bits(bits(x_after), bits(x)), mode
+
+
+def test_gemm_dec_ex_refusals(ctx):
+    """The hook's host checks: -1 (or -4 for a type the engine never runs)
+    before any launch."""
+    a, w = dr.gemm_inputs(0, 3, 64, 64)
+    codes, scales = dr.mx_dec_weights(0, 64, 64)
+    bias = np.zeros(64, np.float32)
+    res = np.zeros((3, 64), np.float32)
+    fuse = dict(x_in=a[0], w=a[1], b=a[2], active=1)
+    ex = ctx.test_gemm_dec_ex
+    ex(a, w, bf16=True, mode=3, bias=bias)
+    ex(a, wq=codes, ws=scales, bf16=True, mode=2, res=res)
+    bad = [dict(a=a[:, :48], w=w[:, :48], mode=1),                       # K % 32
+           dict(a=a, w=w[:48], mode=3, bias=bias[:48]),                  # N % 32, packed
+           dict(a=a[:2], w=w, mode=0, ln=fuse),                          # ln, M != 1
+           dict(w=w, mode=1, ln=fuse),                                   # ln, mode 1
+           dict(w=w, mode=0, ln=dict(fuse, P=np.zeros((9, 64), np.float32), pbias=bias)),  # KS 9
+           dict(w=w, mode=0, ln=dict(fuse, P=np.zeros((2, 64), np.float32))),  # no pbias
+           dict(w=w, mode=1),                                            # no a
+           dict(a=a, wq=codes, mode=1),                                  # no scales
+           dict(a=a, ws=scales, mode=1),                                 # no codes
+           dict(a=a, w=w, mode=3),                                       # no bias, packed
+           dict(a=a, w=w, mode=2),                                       # no residual
+           dict(a=a, w=w, mode=1, bias=bias),                            # a bias EPI_F32 ignores
+           dict(a=a, w=w, mode=4, bias=bias)]
+    for kw in bad:
+        with pytest.raises(ValueError):
+            ex(kw.pop("a", None), kw.pop("w", None), bf16=True, **kw)
+    with pytest.raises(NotImplementedError):                             # w8 is bf16 only
+        ex(a, wq=codes, ws=scales, bf16=False, mode=1)

@@ -412,3 +412,69 @@ def test_mx_round_helper_matches_e4m3_codes():
     E = np.ceil(np.log2(np.maximum(np.abs(h).max(axis=1, keepdims=True), 1e-30) / 448.0))
     ref = _e4m3_decode(_e4m3_encode(h / np.exp2(E))) * np.exp2(E)
     assert np.array_equal(_mx_round(a), ref.reshape(a.shape))
+
+
+def mx_edge_blocks():
+    """Blocks of 32 that random data never produces, one per row: zeros and
+    signed zeros; amax exactly 448 2^e, its float neighbours, and 1.75 2^e
+    with its neighbours (the mantissa at which the block exponent steps);
+    every e4m3 tie (a mantissa ending ...1000: halfway between two codes) of
+    both parities with its float neighbours; the subnormal range below 2^-6
+    of the scale with its ties; amax so small that the exponent clamps at
+    -127, and the largest f32 values (the exponent stays below +127: 448 2^127
+    is no f32, so that clamp cannot be reached from finite input)."""
+    f = np.float32
+    up = lambda v: np.nextafter(f(v), f(np.inf))
+    dn = lambda v: np.nextafter(f(v), f(-np.inf))
+    rows = [np.zeros(32, f), np.where(np.arange(32) % 2, f(-0.0), f(0.0)).astype(f)]
+    fill = np.asarray([(-1) ** j * (j + 1) / 64 for j in range(31)], f)  # below every amax used
+    for e in (-135, -127, -126, -20, -1, 0, 7, 60, 118, 119):
+        for base in (448.0, 1.75):
+            top = np.ldexp(f(base), e)
+            if not np.isfinite(top) or top == 0:
+                continue
+            for amax in (top, up(top), dn(top), -top):
+                rows.append(np.concatenate([[amax], fill * np.abs(top) / f(8)]).astype(f))
+    # ties between normal codes, under amax = 448 2^e (block exponent e)
+    ties = [(8 + man + 0.5) * 2.0 ** (ex - 10) for ex in range(1, 16) for man in range(8)]
+    ties = np.asarray([t for t in ties if t < 448.0], f)
+    sub = np.asarray([(k + 0.5) * 2.0 ** -9 for k in range(8)] +
+                     [k * 2.0 ** -9 for k in range(9)] + [2.0 ** -11, 2.0 ** -12], f)
+    vals = np.concatenate([ties, up(ties), dn(ties), sub, up(sub), dn(sub[sub > 0])])
+    vals = np.concatenate([vals, -vals])
+    for e in (-40, 0, 9):
+        for i in range(0, len(vals), 31):
+            blk = np.zeros(32, f)
+            blk[0] = 448.0
+            blk[1:1 + len(vals[i:i + 31])] = vals[i:i + 31]
+            rows.append(np.ldexp(blk, e).astype(f))
+    fmax, tiny = np.finfo(f).max, f(2.0 ** -149)
+    for amax in (tiny, f(2.0 ** -140), f(2.0 ** -127), np.ldexp(f(448.0), -128), fmax, f(2.0 ** 127)):
+        rows.append(np.concatenate([[amax, -amax, amax / f(2), amax / f(3)], np.zeros(28, f)]).astype(f))
+    return np.stack(rows)
+
+
+def test_mx_quantize_rows_equals_the_reference_encoder():
+    """The load-time quantizer (mx_quantize_row through mwx_test_mx_quantize_rows)
+    against encoder_ref.mx_encode, codes and scales bit for bit: random rows
+    over 60 binades and the edge blocks above. Both follow the stated rule:
+    the smallest e with amax <= 448 2^e, round to nearest even, no clipping."""
+    import encoder_ref as er
+    rng = np.random.default_rng(5)
+    x = rng.standard_normal((64, 256)).astype(np.float32)
+    x *= np.ldexp(np.float32(1.0), rng.integers(-30, 30, (64, 8))).repeat(32, axis=1)
+    edge = mx_edge_blocks()
+    assert np.isfinite(edge).all()
+    for name, data in (("random", x), ("edge", edge)):
+        q, s = mwx.mx_quantize_rows(data)
+        qr, sr = er.mx_encode(data)
+        bad = np.flatnonzero((s != sr).reshape(-1))
+        assert bad.size == 0, (name, "scale", bad[:8], s.reshape(-1)[bad[:8]], sr.reshape(-1)[bad[:8]])
+        bad = np.argwhere(q != qr)
+        assert bad.size == 0, (name, "code", bad[:8], q[q != qr][:8], qr[q != qr][:8])
+        # no clipping needed: no code is the NaN pattern
+        assert ((q & 0x7F) != 0x7F).all()
+    se = mwx.mx_quantize_rows(edge)[1].astype(int).reshape(-1) - 127
+    assert se.min() == -127 and se.max() == 120
+    with pytest.raises(ValueError):
+        mwx.mx_quantize_rows(np.zeros((1, 48), np.float32))
