@@ -161,6 +161,17 @@ typedef struct mwx_token_data {
   float vlen; /* voice length of the token */
 } mwx_token_data;
 
+/* Contextual biasing (INTEGRATION.md "Contextual biasing"): one
+ * boosted phrase. tokens: n_tokens (1 .. MWX_BIAS_MAX_TOKENS) text-token ids,
+ * each in [0, mwx_token_eot); boost: finite, may be negative or zero. */
+#define MWX_BIAS_MAX_TOKENS 16
+#define MWX_BIAS_MAX_PHRASES 1024
+struct mwx_bias_phrase {
+  const mwx_token* tokens;
+  int n_tokens;
+  float boost;
+};
+
 /* Mirrors the whisper_full_params fields the service sets or relies on
  * (src/stt_engine.cpp:214-243) plus the upstream defaults it inherits. */
 struct mwx_full_params {
@@ -259,6 +270,38 @@ struct mwx_full_params {
    * (0, default) detects per chunk; MWX_CHUNK_LANG_RECORDING (1) detects once
    * per recording (rule at mwx_full_batch_chunked). */
   int chunk_language;
+
+  /* Engine extension (appended fields; this project's rule):
+   * contextual biasing. NULL / 0 (default): off, and the call is bit-identical
+   * to one made before the fields existed (same kernels, same step graph).
+   * Else n_bias_phrases (0 .. MWX_BIAS_MAX_PHRASES) phrases the decoders
+   * should prefer. For a decoder, h is the ids it has generated so far in the
+   * current attempt of the current window, oldest first (prompt and sot
+   * sequence excluded; timestamp tokens included, and as no phrase can hold
+   * one they end a match; a temperature-fallback attempt and a new window
+   * start from the empty h; in beam search and best-of a decoder that takes
+   * over another's candidate takes over its h). The matches of h are the pairs
+   * (p, k), 0 <= k < len_p, k <= |h|, with the last k ids of h equal to the
+   * first k ids of phrase p (k = 0 always matches: a phrase's first token is
+   * boosted at every step). bias[t] = the largest boost_p over the matches
+   * with p[k] == t; a sampling row's raw logits become x'[t] = x[t] + bias[t]
+   * (one float add; tokens no match points at keep their bits) before anything
+   * else reads them. Everything downstream sees x': the temperature division,
+   * the suppression and timestamp rules, p / plog, the draws, and the
+   * no-speech probability of a window's first step (a boost can therefore move
+   * no_speech_prob). A failed match retracts nothing. The matcher tables are
+   * built and uploaded once per call; the state is carried on the device.
+   * Honoured by mwx_full_with_state, mwx_full_batch, _pcm16, _trimmed and
+   * _chunked (every chunk); ignored by mwx_align_batch, the DTW pass and
+   * language detection. Refused before any GPU work and before any state
+   * changes: -3 for an id outside [0, mwx_token_eot); -1 (logged) for
+   * n_bias_phrases outside its range, a non-zero count with a NULL array,
+   * n_tokens outside 1 .. MWX_BIAS_MAX_TOKENS, or a NaN / infinite boost.
+   * mwx_perf_enable class "logits_bias": the kernel's launches. The effect on
+   * recognition and a sensible boost range are unmeasured (no real checkpoint
+   * has been run with it). */
+  const struct mwx_bias_phrase* bias_phrases;
+  int n_bias_phrases;
 };
 #define MWX_CHUNK_LANG_PER_CHUNK 0
 #define MWX_CHUNK_LANG_RECORDING 1
@@ -576,7 +619,8 @@ void mwx_log_set(mwx_log_callback log_callback, void* user_data);
  * Times every launch of one kernel class with a pair of HIP events recorded on
  * the state's stream (the stream the kernels run on). Classes: "mel",
  * "enc_gemm", "enc_attn", "cross_gemm", "dec_gemm", "dec_attn_self",
- * "dec_attn_cross", "logits_gemm", "logits_proc", "prosody". NULL disables.
+ * "dec_attn_cross", "logits_gemm", "logits_bias" (contextual biasing: launched
+ * only by calls with bias_phrases), "logits_proc", "prosody". NULL disables.
  * mwx_perf_read synchronizes, returns the summed milliseconds and the launch
  * count since the last read, and resets them. */
 void mwx_perf_enable(struct mwx_state* state, const char* kernel_class);

@@ -516,6 +516,40 @@ int mwx_test_lang_keep(struct mwx_state* state, int on);
  * (no detection for this state, or keeping off); -1 bad arguments. */
 int mwx_test_lang_last(struct mwx_state* state, float* logits_out, int n);
 
+/* --- contextual biasing (tests/test_bias_ref.py, test_gpu_bias_kernel.py) -- */
+
+/* The matcher tables of n phrases (csrc/bias.h) and the host
+ * transition: needs no context and does no device work. Walks hist [n_hist]
+ * from the root and writes the state's (token, bias) set, tokens ascending,
+ * into tokens_out / boosts_out (room for cap each; nullable with cap 0) and
+ * the tables' size in bytes into *table_bytes_out (nullable). Returns the
+ * set's size (which may exceed cap: then only cap pairs are written), or the
+ * code mwx_full_batch would refuse the phrases with (-1; -3 for a negative id: no
+ * vocabulary is known here), or -1 for n_hist < 0 or
+ * hist == NULL with n_hist > 0. */
+int mwx_test_bias_match(const struct mwx_bias_phrase* phrases, int n,
+                        const mwx_token* hist, int n_hist, mwx_token* tokens_out,
+                        float* boosts_out, int cap, long long* table_bytes_out);
+
+/* The id of that state (root = 0; ids are breadth-first over the phrases'
+ * trie), as the host's walk gives it; the refusal codes of mwx_test_bias_match. */
+int mwx_test_bias_state(const struct mwx_bias_phrase* phrases, int n, const mwx_token* hist,
+                        int n_hist);
+
+/* One logits_bias launch (csrc/k_bias.hip) on R rows of V logits [R][V]. Rows
+ * start at the root; a small kernel walks row r's history hist[r][0 ..
+ * hist_len[r]) (hist is [R][H]) with the __device__ transition the advance
+ * kernels use, then logits_bias runs once with active [R] and sample [R].
+ * Out: logits_out [R][V], state_out [R]. The hook owns the device buffers;
+ * both outputs lie between two guard bands of sentinel words. Returns 0; -1
+ * without a launch for a null argument, R outside 1..256, V < 1, H < 0, a
+ * hist_len outside 0..H, or phrases mwx_full_batch would refuse (ids checked
+ * against V); -2 on a device error; -3 if a launch changed a guard band. */
+int mwx_test_logits_bias(struct mwx_context* ctx, const struct mwx_bias_phrase* phrases, int n,
+                         int R, int V, const float* logits, const mwx_token* hist, int H,
+                         const int* hist_len, const int* active, const int* sample,
+                         float* logits_out, int* state_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -683,6 +683,28 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
   }
   const int n_max = P.bench_fixed_steps > 0 ? P.bench_fixed_steps : hp.n_text_ctx / 2 - 4;
 
+  // ---------------- contextual biasing (D14) ----------------
+  // the call's matcher tables, built and uploaded once, before the first
+  // window (validated by the caller: bias_check); the alignment pass and the
+  // detection above run without them. bias_state: the state after a row's
+  // generated ids (only the last MWX_BIAS_MAX_TOKENS can matter), the host's
+  // side of RowRun.pad / RowCtl.pad[0]
+  std::vector<int32_t> bias_tab;
+  if (!align && P.bias_phrases && P.n_bias_phrases > 0) {
+    bias_tab = bias_build(P.bias_phrases, P.n_bias_phrases);
+    int* d_bt = (int*)S.bias_tab.get(bias_tab.size() * 4);
+    HIPC(hipMemcpyAsync(d_bt, bias_tab.data(), bias_tab.size() * 4, hipMemcpyHostToDevice, st));
+    D.bias_dev = d_bt;
+  }
+  auto bias_state = [&](const std::vector<mwx_token_data>& toks) {
+    if (bias_tab.empty()) return 0;
+    int s = 0;
+    for (size_t i = toks.size() > MWX_BIAS_MAX_TOKENS ? toks.size() - MWX_BIAS_MAX_TOKENS : 0;
+         i < toks.size(); ++i)
+      s = bias_next_state(bias_tab.data(), s, toks[i].id);
+    return s;
+  };
+
   // ---------------- transcript alignment (D12) ----------------
   if (align) {
     // the clips mwx_full_batch would decode a window of, at seek 0
@@ -942,6 +964,7 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
           k.want_probs = host_probs ? 1 : 0;
           k.temperature = t_cur;
           k.want_nosp = (k.sample && k.is_initial) ? 1 : 0;
+          k.pad[0] = bias_state(w.tokens);
         }
       };
       // run-ahead (every decode mode: greedy, temperature sampling, beam
@@ -1171,6 +1194,7 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
           x.seek = cr.seek;
           x.seek_end = cr.seek_end;
           x.sum = w.sum_logprobs_all;
+          x.pad = bias_state(w.tokens);
           std::copy(cr.prompt.begin(), cr.prompt.end(), rp + (size_t)r * D.Tctx);
         }
         constexpr int NS = State::RUN_SLOTS;
@@ -1252,6 +1276,7 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
         rc.prompt_stride = D.Tctx;
         rc.temperature = t_cur;
         rc.want_probs = host_probs ? 1 : 0;
+        rc.bias = D.bias_dev;
         for (int i = 0; i < NS; ++i)
           if (!S.ev_step[i]) HIPC(hipEventCreateWithFlags(&S.ev_step[i], hipEventDisableTiming));
         bool instr_of[NS] = {};
@@ -1754,7 +1779,8 @@ void mwx_free_state(struct mwx_state* state) {
                        &S.pf_in, &S.pf_x, &S.pf_h, &S.pf_o, &S.pf_ff, &S.pf_pqkv,
                        &S.pf_pres, &S.pf_pq, &S.perf_span,
                        &S.dtw_kself, &S.dtw_vself, &S.dtw_w, &S.dtw_cost, &S.dtw_frames,
-                       &S.dtw_meta, &S.xkeys, &S.sc_in, &S.sc_h, &S.sc_logits, &S.sc_out};
+                       &S.dtw_meta, &S.xkeys, &S.sc_in, &S.sc_h, &S.sc_logits, &S.sc_out,
+                       &S.bias_tab};
   for (auto* b : bufs) b->release();
   if (S.pin) (void)hipHostFree(S.pin);
   S.pin = nullptr;
@@ -1838,6 +1864,8 @@ struct mwx_full_params mwx_full_default_params(int strategy) {
   p.abort_callback = nullptr;
   p.abort_callback_user_data = nullptr;
   p.bench_fixed_steps = 0;
+  p.bias_phrases = nullptr;
+  p.n_bias_phrases = 0;
   return p;
 }
 
@@ -1858,6 +1886,14 @@ static bool lang_ids_ok(const Vocab& vb, const int* lang_ids, int n) {
     if (lang_ids[b] > lang_max_id()) return false;
   return true;
 }
+// mwx_full_params.bias_phrases (mwx.h; DESIGN.md D14): 0, or the code the call
+// returns before it touches a state or the device
+static int bias_check(const Vocab& vb, const mwx_full_params& P, const char* fn) {
+  const char* why = "";
+  const int rc = bias_validate(P.bias_phrases, P.n_bias_phrases, vb.token_eot, &why);
+  if (rc == -1) MWX_LOG_ERROR("%s: bias_phrases: %s\n", fn, why);
+  return rc;
+}
 }  // namespace mwx
 
 static int full_batch_any(struct mwx_context* ctx, struct mwx_state* const* states,
@@ -1867,6 +1903,7 @@ static int full_batch_any(struct mwx_context* ctx, struct mwx_state* const* stat
   for (int c = 0; c < n_clips; ++c)
     if (!states[c] || (n_samples[c] > 0 && !samples[c])) return -1;
   if (!mwx::lang_ids_ok(ctx->c.vocab, params.lang_ids, n_clips)) return -3;
+  if (int rc = mwx::bias_check(ctx->c.vocab, params, "mwx_full_batch")) return rc;
   try {
     HIPC(hipSetDevice(ctx->c.device));
     if (ctx->c.wtype == mwx::GGML_BF16)
@@ -1970,6 +2007,7 @@ int mwx_full_batch_trimmed(struct mwx_context* ctx, struct mwx_state* const* sta
                            const struct mwx_vad_trimmed* const* trimmed, const int* clip_index,
                            int n_clips) {
   if (!ctx || !states || !trimmed || !clip_index || n_clips <= 0) return -1;
+  if (int rc = mwx::bias_check(ctx->c.vocab, params, "mwx_full_batch_trimmed")) return rc;
   std::vector<mwx_state*> run_states;
   std::vector<const void*> ptrs;
   std::vector<int> lens;
@@ -2027,6 +2065,7 @@ int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* sta
                            const struct mwx_vad_trimmed* const* trimmed, const int* clip_index,
                            int n_clips, int max_batch) {
   if (!ctx || !states || !trimmed || !clip_index || n_clips <= 0 || max_batch < 1) return -1;
+  if (int rc = mwx::bias_check(ctx->c.vocab, params, "mwx_full_batch_chunked")) return rc;
   struct Job {
     int entry;
     int64_t chunk;
@@ -4163,4 +4202,54 @@ extern "C" int mwx_test_lang_last(struct mwx_state* state, float* logits_out, in
   const std::vector<float>& ll = state->s.lang_last;
   if (!ll.empty()) memcpy(logits_out, ll.data(), ll.size() * 4);
   return (int)ll.size();
+}
+
+// ---------------------------------------------------------------------------
+// Contextual biasing on given data (k_bias.hip; mwx_test_bias_match is in
+// bias.cpp: it needs no device)
+// ---------------------------------------------------------------------------
+extern "C" int mwx_test_logits_bias(struct mwx_context* ctx, const struct mwx_bias_phrase* phrases,
+                                    int n, int R, int V, const float* logits,
+                                    const mwx_token* hist, int H, const int* hist_len,
+                                    const int* active, const int* sample, float* logits_out,
+                                    int* state_out) {
+  if (!ctx || !logits || !hist_len || !active || !sample || !logits_out || !state_out) return -1;
+  if (R < 1 || R > 256 || V < 1 || H < 0 || (H > 0 && !hist) || n < 1) return -1;
+  for (int r = 0; r < R; ++r)
+    if (hist_len[r] < 0 || hist_len[r] > H) return -1;
+  if (mwx::bias_validate(phrases, n, V) != 0) return -1;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    const std::vector<int32_t> tab = mwx::bias_build(phrases, n);
+    std::vector<mwx::RowCtl> hc(R);
+    for (int r = 0; r < R; ++r) {
+      memset(&hc[r], 0, sizeof(mwx::RowCtl));
+      hc[r].active = active[r];
+      hc[r].sample = sample[r];
+    }
+    DevScratch m;
+    int* dt = (int*)m.get(tab.size() * 4);
+    int* dh = (int*)m.get(std::max<size_t>(1, (size_t)R * H) * 4);
+    int* dn = (int*)m.get((size_t)R * 4);
+    mwx::RowCtl* dc = (mwx::RowCtl*)m.get((size_t)R * sizeof(mwx::RowCtl));
+    HIPC(hipMemcpy(dt, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    if (H > 0) HIPC(hipMemcpy(dh, hist, (size_t)R * H * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dn, hist_len, (size_t)R * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dc, hc.data(), (size_t)R * sizeof(mwx::RowCtl), hipMemcpyHostToDevice));
+    GuardedBuf gl, gs;
+    float* dl = (float*)gl.make(m, (size_t)R * V * 4, logits);
+    int* ds = (int*)gs.make(m, (size_t)R * 4, nullptr);
+    mwx::bias_walk_rows(dt, dh, dn, H, R, dc, ds, nullptr);
+    if (!mwx::logits_bias(dl, dc, dt, R, V, nullptr)) return -1;
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    std::vector<float> hl((size_t)R * V);
+    std::vector<int> hs((size_t)R);
+    if (!gl.take(hl.data()) || !gs.take(hs.data())) return -3;
+    memcpy(logits_out, hl.data(), hl.size() * 4);
+    memcpy(state_out, hs.data(), hs.size() * 4);
+    return 0;
+  } catch (...) {
+    return -2;
+  }
 }

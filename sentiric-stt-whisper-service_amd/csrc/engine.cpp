@@ -27,6 +27,7 @@
 #include <thread>
 #include <vector>
 
+#include "bias.h"
 #include "common.h"
 #include "kernels.h"
 #include "vad_trim.h"
@@ -268,6 +269,7 @@ struct State {
   // run-ahead attempts redone on the host loop (mwx_test_runahead_fallbacks)
   long n_ra_fallback = 0;
   DBuf lpflt, lpparts, lpres;  // logits-processing scratch
+  DBuf bias_tab;               // contextual biasing: the call's matcher tables (bias.h)
   // beam search KV hand-over without copies: per row, positions below
   // kvown[row] are read from row kvmap[row][pos] (host copies in kvmap_h/kvown_h)
   DBuf kvmap, kvown;
@@ -934,6 +936,9 @@ struct Driver {
   LogitsConst LC;
   // run-ahead: the step's lp_pick runs inside the advance kernel (pick_in())
   bool pick_in_advance = false;
+  // contextual biasing: the call's matcher tables on the
+  // device, set for the window loop only; nullptr = no phrases, no launch
+  const int* bias_dev = nullptr;
   PickIn pick_in() const {
     PickIn p;
     p.logits = (const float*)S.logits.p;
@@ -1975,6 +1980,12 @@ struct Driver {
     if (want_probs) {
       pr = (float*)S.probs.get((size_t)R * V * 4) + (size_t)r0 * V;
       lp = (float*)S.logprobs.get((size_t)R * V * 4) + (size_t)r0 * V;
+    }
+    if (bias_dev) {  // (a call without phrases captures the same graph as ever)
+      PerfScope pb(S, "logits_bias", s);
+      if (!logits_bias((float*)S.logits.p + (size_t)r0 * V, (const RowCtl*)S.ctl.p + r0, bias_dev, n,
+                       V, s))
+        throw std::runtime_error("mwx: logits_bias refused its launch");
     }
     PerfScope ps(S, "logits_proc", s);
     logits_process((float*)S.logits.p + (size_t)r0 * V, (const float*)S.smask.p,

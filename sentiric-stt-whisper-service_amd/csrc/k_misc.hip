@@ -10,6 +10,8 @@
 
 #include <cstdlib>
 
+#define MWX_BIAS_NO_HOST  // (the transition only)
+#include "bias.h"
 #include "kcommon.h"
 #include "kernels.h"
 #include "ln_core.h"
@@ -586,6 +588,7 @@ __device__ __forceinline__ void token_rules(RowRun& w, int id, const RunConst& C
   w.penult_id = w.last_id;
   w.last_id = id;
   w.ntok = i + 1;
+  w.pad = bias_next_state(C.bias, w.pad, id);  // contextual biasing (0 without phrases)
   bool stop = false;
   if (id > C.beg) {
     const int sd_new = 2 * (id - C.beg);
@@ -622,7 +625,8 @@ __device__ __forceinline__ RowCtl next_inputs(const RowRun& w, const RunConst& C
   n.want_probs = C.want_probs;
   n.temperature = C.temperature;
   n.want_nosp = (n.sample && n.is_initial) ? 1 : 0;
-  n.pad[0] = n.pad[1] = 0;
+  n.pad[0] = w.pad;  // the biasing state the step's logits are boosted in
+  n.pad[1] = 0;
   return n;
 }
 
@@ -800,6 +804,7 @@ __global__ __launch_bounds__(BA_T) void beam_advance_kernel(RowRun* __restrict__
           }
         w.ntok = p.ntok;
         w.last_id = p.last_id;
+        w.pad = p.pad;
         w.penult_id = p.penult_id;
         w.has_ts = p.has_ts;
         w.seek_delta = p.seek_delta;

@@ -329,7 +329,7 @@ struct RowCtl {
   int want_probs;    // write probs/logprobs rows (sampling path)
   float temperature; // > 0: logits /= temperature
   int want_nosp;     // compute no_speech probability from the raw logits
-  int pad[2];
+  int pad[2];        // pad[0]: the row's contextual-biasing state (bias.h; 0 = root / off)
 };
 struct TokOut {
   int id;
@@ -359,15 +359,16 @@ struct RowRun {
   int seek, seek_end;  // the clip's window position and end (centiseconds)
   int cls;          // beam: token-sequence class (equal sequences <=> equal cls)
   int used;         // beam: uniforms of the row's RNG consumed so far
-  int pad;
+  int pad;          // contextual biasing: the matcher state after the generated ids (bias.h)
   double sum;       // beam: sum_logprobs_all
 };
 struct RunConst {
   int beg, eot, max_tokens, n_max, delta_min, R, nslot, prompt_stride;
   float temperature;
   int want_probs;
-  int pad[2];
+  const int* bias;  // contextual biasing: the call's matcher tables (bias.h), nullptr = off
 };
+static_assert(sizeof(RunConst) == 48, "the tables pointer takes the former pad words");
 // what the host reads back per row and step (written straight into pinned
 // host memory by the advance kernel: no copy launch per step)
 struct RunReport {
@@ -460,6 +461,18 @@ struct LPScratch {
 void logits_process(float* logits, const float* static_mask, const RowCtl* ctl, TokOut* out,
                     float* probs, float* logprobs, const LogitsConst& C, int R, LPScratch ws,
                     hipStream_t st, bool pick = true);
+
+// Contextual biasing (k_bias.hip): for every row r with
+// ctl[r].active && ctl[r].sample, logits[r V + t] += bias[t] for the tokens the
+// row's matcher state ctl[r].pad[0] points at (tables: bias.h, device copy).
+// Each (row, token) is written by one thread; other rows and entries keep their
+// bits. false (no launch) for a null pointer, R < 1 or V < 1.
+bool logits_bias(float* logits, const RowCtl* ctl, const int* tables, int R, int V,
+                 hipStream_t st);
+// (test hook) state[r] = ctl[r].pad[0] = the state after hist[r][0 .. hist_len[r])
+// from the root, by the device transition of the advance kernels
+void bias_walk_rows(const int* tables, const int* hist, const int* hist_len, int H, int R,
+                    RowCtl* ctl, int* state, hipStream_t st);
 
 // Transcript scoring (k_score.hip): for every row r with
 // active[r] (nullptr: all), from its raw logits x = logits + r V:

@@ -114,6 +114,7 @@ void* mwx_stt_new(const char* model_dir, const char* model_filename, int paralle
   s.gpu_device = gpu_device;
   try {
     settings_dtw_from_env(s);
+    settings_hotwords_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -140,6 +141,7 @@ void* mwx_stt_new_batched(const char* model_dir, const char* model_filename,
   s.batch_window_us = batch_window_us;
   try {
     settings_dtw_from_env(s);
+    settings_hotwords_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -175,6 +177,7 @@ void* mwx_stt_new_ex(const char* model_dir, const char* model_filename, int para
   s.stream_buffer_samples = stream_buffer_samples;
   try {
     settings_dtw_from_env(s);
+    settings_hotwords_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -206,6 +209,7 @@ void* mwx_stt_new_vad(const char* model_dir, const char* model_filename, int par
   s.vad_threshold = vad_threshold;
   try {
     settings_dtw_from_env(s);
+    settings_hotwords_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -237,6 +241,7 @@ void* mwx_stt_new_vad_trim(const char* model_dir, const char* model_filename,
   s.vad_trim = vad_trim != 0;
   try {
     settings_dtw_from_env(s);
+    settings_hotwords_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -272,6 +277,7 @@ void* mwx_stt_new_stream_vad(const char* model_dir, const char* model_filename,
   s.stream_endpoint_silence_ms = stream_endpoint_silence_ms;
   try {
     settings_dtw_from_env(s);
+    settings_hotwords_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());

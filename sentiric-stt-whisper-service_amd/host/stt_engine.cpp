@@ -169,6 +169,14 @@ std::string SpeakerClusterer::assign_or_add(const std::vector<float>& vec) {
   return id;
 }
 
+void settings_hotwords_from_env(Settings& s) {
+  if (const char* v = std::getenv("STT_WHISPER_SERVICE_HOTWORD_BOOST")) {
+    char* end = nullptr;
+    const float b = std::strtof(v, &end);
+    if (end != v && std::isfinite(b) && b >= 0.0f) s.hotword_boost = b;
+  }
+}
+
 void settings_dtw_from_env(Settings& s) {
   static const char* const kPresets[] = {"none", "n_top_most", "custom", "tiny.en", "tiny",
                                          "base.en", "base", "small.en", "small", "medium.en",
@@ -299,7 +307,14 @@ std::string SttEngine::options_key(const RequestOptions& o) const {
   char buf[96];
   std::snprintf(buf, sizeof buf, "%d|%.9g|%d|%d|%d|", beam, temp, best_of, (int)o.translate,
                 (int)o.enable_diarization);
-  return std::string(buf) + lang + "|" + o.prompt;
+  std::string key = std::string(buf) + lang + "|" + o.prompt;
+  if (!o.hotwords.empty()) {  // (no hotwords: the key as it always was)
+    char hb[48];
+    std::snprintf(hb, sizeof hb, "|hw%.9g", hotword_boost_of(o));
+    key += hb;
+    for (const std::string& w : o.hotwords) key += "|" + std::to_string(w.size()) + ":" + w;
+  }
+  return key;
 }
 
 std::vector<TranscriptionResult> SttEngine::transcribe_batched(
@@ -386,7 +401,8 @@ void SttEngine::batcher_loop(std::vector<mwx_state*> states) {
           if (!r->options.should_abort || !r->options.should_abort()) return false;
         return true;
       };
-    const mwx_full_params p = make_params(batch[0]->options, lang, abort_fn);
+    BiasKeep bias_keep;  // (the hotword phrases' arrays, alive for the call)
+    const mwx_full_params p = make_params(batch[0]->options, lang, abort_fn, bias_keep);
     std::vector<const float*> ptrs;
     std::vector<int> lens;
     for (auto& r : batch) {
@@ -455,8 +471,51 @@ std::vector<TranscriptionResult> SttEngine::transcribe_pcm16(const std::vector<i
 }
 
 // Parameter mapping of src/stt_engine.cpp:204-243.
+// Contextual biasing (mwx_full_params.bias_phrases): the boost
+// the request resolves to, and its hotwords as phrases.
+float SttEngine::hotword_boost_of(const RequestOptions& o) const {
+  if (o.hotwords.empty()) return 0.0f;
+  const float b = o.hotword_boost >= 0.0f ? o.hotword_boost : settings_.hotword_boost;
+  return std::isfinite(b) ? b : 0.0f;
+}
+
+void SttEngine::make_bias(const RequestOptions& options, BiasKeep& keep) const {
+  keep.toks.clear();
+  keep.phrases.clear();
+  const float boost = hotword_boost_of(options);
+  if (boost == 0.0f) return;  // (off: nothing is passed)
+  if (!mwx_tokenize) {
+    std::fprintf(stderr, "SttEngine: hotwords ignored: the library has no mwx_tokenize\n");
+    return;
+  }
+  for (const std::string& w : options.hotwords) {
+    if (w.empty()) continue;
+    // two phrases per hotword: after a space (mid-sentence) and bare
+    std::vector<std::vector<mwx_token>> forms;
+    bool ok = true;
+    for (const std::string& text : {" " + w, w}) {
+      std::vector<mwx_token> t(MWX_BIAS_MAX_TOKENS + 1);
+      const int n = mwx_tokenize(ctx_, text.c_str(), t.data(), (int)t.size());
+      if (n < 1 || n > MWX_BIAS_MAX_TOKENS) {
+        ok = false;
+        break;
+      }
+      t.resize(n);
+      forms.push_back(std::move(t));
+    }
+    if (!ok || keep.toks.size() + 2 > (size_t)MWX_BIAS_MAX_PHRASES) {
+      std::fprintf(stderr,
+                   "SttEngine: hotword \"%s\" dropped (no tokens, more than %d tokens, or more "
+                   "than %d phrases)\n", w.c_str(), MWX_BIAS_MAX_TOKENS, MWX_BIAS_MAX_PHRASES);
+      continue;
+    }
+    for (auto& t : forms) keep.toks.push_back(std::move(t));
+  }
+  for (const auto& t : keep.toks) keep.phrases.push_back({t.data(), (int)t.size(), boost});
+}
+
 mwx_full_params SttEngine::make_params(const RequestOptions& options, std::string& target_lang,
-                                       std::function<bool()>& abort_fn) const {
+                                       std::function<bool()>& abort_fn, BiasKeep& bias) const {
   const int beam = options.beam_size >= 0 ? options.beam_size : settings_.beam_size;
   const float temp = options.temperature >= 0.0f ? options.temperature : settings_.temperature;
   const int best_of = options.best_of >= 0 ? options.best_of : settings_.best_of;
@@ -490,6 +549,11 @@ mwx_full_params SttEngine::make_params(const RequestOptions& options, std::strin
   p.audio_ctx_fit = settings_.audio_ctx_fit;
   p.chunk_language =
       settings_.chunk_language_recording ? MWX_CHUNK_LANG_RECORDING : MWX_CHUNK_LANG_PER_CHUNK;
+  make_bias(options, bias);
+  if (!bias.phrases.empty()) {
+    p.bias_phrases = bias.phrases.data();
+    p.n_bias_phrases = (int)bias.phrases.size();
+  }
   return p;
 }
 
@@ -742,7 +806,8 @@ std::vector<TranscriptionResult> SttEngine::transcribe_impl(const std::vector<fl
   const auto t_acq = std::chrono::steady_clock::now();
   std::string lang;
   std::function<bool()> abort_fn = options.should_abort;
-  const mwx_full_params p = make_params(options, lang, abort_fn);
+  BiasKeep bias_keep;  // (the hotword phrases' arrays, alive for the call)
+  const mwx_full_params p = make_params(options, lang, abort_fn, bias_keep);
   int ret;
   if (trimmed) {
     TrimList obj(1);
@@ -796,7 +861,8 @@ std::vector<AlignmentResult> SttEngine::align_run(mwx_state* const* states,
   }
   std::string lang;
   std::function<bool()> abort_fn = options.should_abort;
-  const mwx_full_params p = make_params(options, lang, abort_fn);
+  BiasKeep bias_keep;  // (the hotword phrases' arrays, alive for the call)
+  const mwx_full_params p = make_params(options, lang, abort_fn, bias_keep);
   std::vector<const float*> ptrs;
   std::vector<int> lens, ntok;
   std::vector<const mwx_token*> tptr;
@@ -924,7 +990,8 @@ std::vector<std::pair<std::string, float>> SttEngine::detect_language(
   auto run = [&](mwx_state* state) -> int {
     std::string lang;
     std::function<bool()> abort_fn = nullptr;
-    mwx_full_params p = make_params(RequestOptions(), lang, abort_fn);
+    BiasKeep bias_keep;  // (the hotword phrases' arrays, alive for the call)
+    mwx_full_params p = make_params(RequestOptions(), lang, abort_fn, bias_keep);
     p.language = "auto";
     p.detect_language = true;
     const int ret = mwx_full_with_state(ctx_, state, p, pcm.data(), static_cast<int>(pcm.size()));
@@ -1087,7 +1154,8 @@ std::vector<std::vector<TranscriptionResult>> SttEngine::transcribe_batch(
   }
   std::string lang;
   std::function<bool()> abort_fn = options.should_abort;
-  const mwx_full_params p = make_params(options, lang, abort_fn);
+  BiasKeep bias_keep;  // (the hotword phrases' arrays, alive for the call)
+  const mwx_full_params p = make_params(options, lang, abort_fn, bias_keep);
   int ret;
   if (trimmed) {
     TrimList objs(run.size());

@@ -118,6 +118,11 @@ struct Settings {
   // transcribed in it (mwx_full_params.chunk_language =
   // MWX_CHUNK_LANG_RECORDING). Off: every chunk detects its own language.
   bool chunk_language_recording = false;
+  // Contextual biasing (mwx_full_params.bias_phrases; DESIGN.md D14,
+  // INTEGRATION.md "Contextual biasing"): the boost of a request's hotwords
+  // when the request does not give one. 0 (default): biasing off. The effect
+  // on recognition and a sensible range are unmeasured.
+  float hotword_boost = 0.0f;
   // Streaming VAD for StreamSession (INTEGRATION.md "Streaming"),
   // both off by default and inert without a loaded VAD model or against a
   // library that lacks the mwx_vad_stream_* calls.
@@ -144,6 +149,9 @@ struct Settings {
 // STT_WHISPER_SERVICE_DTW_AHEADS ("layer:head,layer:head,..."). Unset
 // variables leave the fields as they are.
 void settings_dtw_from_env(Settings& s);
+// STT_WHISPER_SERVICE_HOTWORD_BOOST (a finite number >= 0) into
+// Settings::hotword_boost; unset or malformed leaves the field as it is.
+void settings_hotwords_from_env(Settings& s);
 
 // Owner of one mwx_vad_trimmed (vad_trim; defined in stt_engine.cpp).
 struct TrimmedAudio;
@@ -212,6 +220,13 @@ struct RequestOptions {
   int best_of = -1;
   ProsodyOptions prosody_opts;
   std::function<bool()> should_abort = nullptr;
+  // Contextual biasing: words or short phrases the recogniser should prefer.
+  // Each becomes two boosted phrases (" word" and "word", through
+  // mwx_tokenize); one that tokenizes to nothing or to more than
+  // MWX_BIAS_MAX_TOKENS tokens is dropped with a warning. hotword_boost < 0:
+  // Settings::hotword_boost. A boost of 0 passes nothing to the engine.
+  std::vector<std::string> hotwords;
+  float hotword_boost = -1.0f;
 };
 
 struct TranscriptionResult {
@@ -268,6 +283,11 @@ class SttEngine {
   ~SttEngine();
   SttEngine(const SttEngine&) = delete;
   SttEngine& operator=(const SttEngine&) = delete;
+
+  // Everything the engine parameters read from the request: requests with
+  // equal keys share one batched engine call. Hotwords and their boost are
+  // part of it only when there are hotwords.
+  std::string options_key(const RequestOptions& o) const;
 
   bool is_ready() const { return ctx_ != nullptr; }
   const Settings& get_settings() const { return settings_; }
@@ -414,7 +434,6 @@ class SttEngine {
                                                       PerformanceMetrics* out_metrics,
                                                       std::shared_ptr<TrimmedAudio> trimmed);
   void batcher_loop(std::vector<mwx_state*> states);
-  std::string options_key(const RequestOptions& o) const;
   std::deque<std::shared_ptr<Pending>> queue_;
   std::mutex q_mutex_;
   std::condition_variable q_cv_;     // batcher: new work / stop
@@ -425,8 +444,16 @@ class SttEngine {
 
   mwx_state* acquire_state();
   void release_state(mwx_state* state);
+  // the arrays mwx_full_params.bias_phrases points into: alive as long as the
+  // parameters are in use
+  struct BiasKeep {
+    std::vector<std::vector<mwx_token>> toks;
+    std::vector<mwx_bias_phrase> phrases;
+  };
+  float hotword_boost_of(const RequestOptions& o) const;
+  void make_bias(const RequestOptions& options, BiasKeep& keep) const;
   mwx_full_params make_params(const RequestOptions& options, std::string& target_lang,
-                              std::function<bool()>& abort_fn) const;
+                              std::function<bool()>& abort_fn, BiasKeep& bias) const;
   std::vector<TranscriptionResult> collect(mwx_state* state, const std::string& lang,
                                            const float* pcm, size_t pcm_size,
                                            const ProsodyOptions& popts, int* token_count) const;

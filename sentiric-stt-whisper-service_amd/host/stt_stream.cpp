@@ -77,7 +77,7 @@ void StreamSession::restart_buffer(size_t keep_from) {
 
 std::vector<TranscriptionResult> StreamSession::transcribe(const std::vector<int16_t>& pcm,
                                                            SttEngine::PerformanceMetrics* perf) {
-  RequestOptions options;  // the stream path uses default request options
+  const RequestOptions& options = options_;  // default request options (+ set_hotwords)
   if (!gate_from_stream_) return engine_.transcribe_pcm16(pcm, 16000, options, perf);
   // the whole buffer: every probability, the provisional one included; a
   // prefix that ends on a chunk boundary: its whole chunks (rule D6 either way)

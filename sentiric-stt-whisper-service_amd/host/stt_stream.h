@@ -86,6 +86,14 @@ class StreamSession {
 
   size_t buffered_samples() const { return buffer_.size(); }
 
+  // The request options of the session's transcriptions (default: none set).
+  // The stream path reads the contextual-biasing fields (hotwords,
+  // hotword_boost); the rest stay at the reference's stream defaults.
+  void set_hotwords(const std::vector<std::string>& hotwords, float hotword_boost = -1.0f) {
+    options_.hotwords = hotwords;
+    options_.hotword_boost = hotword_boost;
+  }
+
   static constexpr size_t kMaxBufferSamples = 16000 * 30;  // src/grpc_server.cpp:132
 
  private:
@@ -98,6 +106,7 @@ class StreamSession {
   void drop_vad();               // a failed VAD stream call: the session goes on as without one
 
   SttEngine& engine_;
+  RequestOptions options_;  // default request options (+ set_hotwords)
   std::shared_ptr<VadStreamHandle> vad_;  // Settings::stream_vad / stream_endpoint_silence_ms
   bool gate_from_stream_ = false;
   bool endpoint_ = false;

@@ -90,6 +90,40 @@ class _Beam(C.Structure):
 
 ABORT_CB = C.CFUNCTYPE(C.c_bool, C.c_void_p)
 
+BIAS_MAX_TOKENS = 16
+BIAS_MAX_PHRASES = 1024
+
+
+class BiasPhrase(C.Structure):
+    """mwx_bias_phrase: one boosted phrase (contextual biasing)."""
+    _fields_ = [("tokens", C.POINTER(C.c_int32)), ("n_tokens", C.c_int), ("boost", C.c_float)]
+
+
+def bias_phrases(phrases):
+    """(array of BiasPhrase or None, objects to keep alive) for an iterable of
+    (token ids, boost). Nothing is checked here: the library refuses bad input."""
+    items = [(np.ascontiguousarray(t, dtype=np.int32).reshape(-1), float(b)) for t, b in phrases]
+    if not items:
+        return None, []
+    arr = (BiasPhrase * len(items))()
+    for i, (t, b) in enumerate(items):
+        arr[i].tokens = t.ctypes.data_as(C.POINTER(C.c_int32))
+        arr[i].n_tokens = len(t)
+        arr[i].boost = b
+    return arr, [arr] + [t for t, _ in items]
+
+
+def with_bias(params: "FullParams", phrases) -> "FullParams":
+    """A copy of params with bias_phrases / n_bias_phrases set to the given
+    (token ids, boost) pairs. The copy keeps the arrays alive (and the
+    caller's params its strings: keep that one too)."""
+    p = FullParams.from_buffer_copy(params)
+    arr, keep = bias_phrases(phrases)
+    p.bias_phrases = arr
+    p.n_bias_phrases = 0 if arr is None else len(arr)
+    p._bias_keep = (keep, params)
+    return p
+
 
 class FullParams(C.Structure):
     _fields_ = [
@@ -114,6 +148,7 @@ class FullParams(C.Structure):
         ("audio_ctx_fit", C.c_bool),
         ("lang_ids", C.POINTER(C.c_int)),
         ("chunk_language", C.c_int),
+        ("bias_phrases", C.POINTER(BiasPhrase)), ("n_bias_phrases", C.c_int),
     ]
 
 
@@ -205,6 +240,41 @@ class Prosody(C.Structure):
 
 
 _lib = None
+
+
+def bias_state(phrases, hist) -> int:
+    """mwx_test_bias_state (host only): the matcher state id after hist."""
+    arr, keep = bias_phrases(phrases)
+    h = np.ascontiguousarray(hist, dtype=np.int32).reshape(-1)
+    fn = lib().mwx_test_bias_state
+    ip = C.POINTER(C.c_int32)
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(BiasPhrase), C.c_int, ip, C.c_int]
+    rc = fn(arr, 0 if arr is None else len(arr), h.ctypes.data_as(ip), len(h))
+    del keep
+    return rc
+
+
+def bias_match(phrases, hist, cap: int = 4096):
+    """mwx_test_bias_match (host only): the matcher tables of the (token ids,
+    boost) pairs, the state after hist from the root. Returns (rc, {token:
+    bias}, table bytes); rc < 0: the refusal code."""
+    arr, keep = bias_phrases(phrases)
+    h = np.ascontiguousarray(hist, dtype=np.int32).reshape(-1)
+    toks = np.zeros(max(cap, 1), np.int32)
+    boosts = np.zeros(max(cap, 1), np.float32)
+    nbytes = C.c_longlong(-1)
+    fn = lib().mwx_test_bias_match
+    ip = C.POINTER(C.c_int32)
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(BiasPhrase), C.c_int, ip, C.c_int, ip, C.POINTER(C.c_float), C.c_int,
+                   C.POINTER(C.c_longlong)]
+    rc = fn(arr, 0 if arr is None else len(arr), h.ctypes.data_as(ip), len(h),
+            toks.ctypes.data_as(ip), boosts.ctypes.data_as(C.POINTER(C.c_float)), cap,
+            C.byref(nbytes))
+    del keep
+    n = max(0, min(rc, cap))
+    return rc, {int(t): np.float32(b) for t, b in zip(toks[:n], boosts[:n])}, nbytes.value
 
 
 def lib() -> C.CDLL:
@@ -991,6 +1061,42 @@ class Context:
         fn.argtypes = [C.c_void_p, C.c_int, C.c_int, fpp, C.c_int, C.c_int, fpp, ip]
         rc = fn(self.ctx, R, V, fptr(logits), t0, n, fptr(probs), best.ctypes.data_as(ip))
         return rc, probs, best
+
+    def test_logits_bias_rc(self, phrases, logits: np.ndarray, hist, active, sample):
+        """mwx_test_logits_bias: phrases as (token ids, boost) pairs, logits
+        [R][V] f32, hist a list of R id lists, active / sample [R]. Returns
+        (rc, logits_out [R][V], state_out [R]); what the call did not write is
+        NaN (state: -1)."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        R, V = logits.shape
+        H = max([len(h) for h in hist] + [1])
+        hh = np.zeros((R, H), np.int32)
+        hl = np.zeros(R, np.int32)
+        for r, h in enumerate(hist):
+            hh[r, :len(h)] = h
+            hl[r] = len(h)
+        active = np.ascontiguousarray(active, dtype=np.int32)
+        sample = np.ascontiguousarray(sample, dtype=np.int32)
+        assert active.shape == (R,) and sample.shape == (R,) and len(hist) == R
+        arr, keep = bias_phrases(phrases)
+        out = np.full((R, V), np.nan, np.float32)
+        state = np.full(R, -1, np.int32)
+        fn = lib().mwx_test_logits_bias
+        fpp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(BiasPhrase), C.c_int, C.c_int, C.c_int, fpp, ip,
+                       C.c_int, ip, ip, ip, fpp, ip]
+        rc = fn(self.ctx, arr, 0 if arr is None else len(arr), R, V, fptr(logits),
+                hh.ctypes.data_as(ip), H, hl.ctypes.data_as(ip), active.ctypes.data_as(ip),
+                sample.ctypes.data_as(ip), fptr(out), state.ctypes.data_as(ip))
+        del keep
+        return rc, out, state
+
+    def test_logits_bias(self, phrases, logits, hist, active, sample):
+        """As test_logits_bias_rc, raising on a non-zero return."""
+        rc, out, state = self.test_logits_bias_rc(phrases, logits, hist, active, sample)
+        self._hook_rc("mwx_test_logits_bias", rc)
+        return out, state
 
     def test_lang_probs(self, logits, t0: int, n: int):
         """As test_lang_probs_rc, raising on a non-zero return."""
