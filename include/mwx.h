@@ -302,6 +302,39 @@ struct mwx_full_params {
    * has been run with it). */
   const struct mwx_bias_phrase* bias_phrases;
   int n_bias_phrases;
+
+  /* Engine extension (appended fields; this project's rule):
+   * constrained decoding. NULL (default): off, and the call is bit-identical to
+   * one made before the fields existed (same kernels, same step graph). Else a
+   * byte-level automaton (mwx_constraint_from_dfa / _from_choices, below) that
+   * every sampling step of every decoder is held to. A decoder carries a state
+   * s: the start state at the beginning of every attempt of every window (in
+   * beam search and best-of a decoder that takes over another's candidate
+   * takes over its state); after it generates id < mwx_token_eot, s becomes
+   * delta*(s, bytes(id)), bytes(id) being mwx_token_to_str's string; any other
+   * id leaves s as it is. At a sampling step in state s != 0 a text token
+   * t < eot is rejected iff bytes(t) is empty or delta*(s, bytes(t)) == 0; eot
+   * is rejected iff s is not accepting; ids above eot (specials, timestamps)
+   * are never rejected. In state 0 (the constraint has failed) nothing is
+   * rejected and decoding goes on unconstrained. A rejected token's logit
+   * becomes y - constraint_penalty, y = x / T (or x): after the temperature
+   * division, before the suppression and timestamp rules. Everything
+   * downstream sees it (p / plog, the timestamp-versus-text rule, the draws);
+   * the no-speech probability, computed from the raw logits, does not. Tokens
+   * that are not rejected keep their bits. The penalty is finite (default 100,
+   * whisper.cpp's grammar_penalty), so the constraint alone never leaves a row
+   * without a finite logit. bias_phrases may be used with it (the boosts add to
+   * the raw logits first). Honoured by mwx_full_with_state, mwx_full_batch,
+   * _pcm16, _trimmed and _chunked (every chunk); ignored by mwx_align_batch,
+   * the DTW pass and language detection. Refused (-1, logged) before any GPU
+   * work and before any state changes: a NaN, infinite or <= 0 penalty with a
+   * non-NULL constraint; bench_fixed_steps > 0 with a constraint.
+   * mwx_perf_enable class "logits_constrain": the mask kernel's launches. One
+   * constraint per call: per-entry constraints, a grammar or regex compiler
+   * and Unicode case folding are not provided. The effect on recognition with
+   * a real checkpoint is unmeasured. */
+  const struct mwx_constraint* constraint;
+  float constraint_penalty;
 };
 #define MWX_CHUNK_LANG_PER_CHUNK 0
 #define MWX_CHUNK_LANG_RECORDING 1
@@ -620,7 +653,8 @@ void mwx_log_set(mwx_log_callback log_callback, void* user_data);
  * the state's stream (the stream the kernels run on). Classes: "mel",
  * "enc_gemm", "enc_attn", "cross_gemm", "dec_gemm", "dec_attn_self",
  * "dec_attn_cross", "logits_gemm", "logits_bias" (contextual biasing: launched
- * only by calls with bias_phrases), "logits_proc", "prosody". NULL disables.
+ * only by calls with bias_phrases), "logits_constrain" (constrained decoding:
+ * only by calls with a constraint), "logits_proc", "prosody". NULL disables.
  * mwx_perf_read synchronizes, returns the summed milliseconds and the launch
  * count since the last read, and resets them. */
 void mwx_perf_enable(struct mwx_state* state, const char* kernel_class);
@@ -831,6 +865,47 @@ int mwx_align_batch(struct mwx_context* ctx, struct mwx_state* const* states,
  * out of range or without rows. Outputs are nullable. */
 int mwx_align_row(struct mwx_state* state, int i, float* plog, mwx_token* top_id,
                   float* top_plog);
+
+/* --- constrained decoding -------------------------------
+ * A constraint is a deterministic automaton over bytes: states 0 .. S - 1
+ * (2 <= S <= MWX_CONSTRAINT_MAX_STATES), state 0 dead (not accepting, every
+ * transition to 0), a start state >= 1, trans [S][256] state ids and an
+ * accepting flag per state. The object is immutable once built, usable from
+ * any thread and with any context, and freed by mwx_constraint_free (not
+ * while a call that uses it runs).
+ *
+ * mwx_constraint_from_dfa returns NULL (reason logged) for n_states outside
+ * 2 .. MWX_CONSTRAINT_MAX_STATES, a null table, a target >= n_states, a state
+ * 0 that is accepting or has a transition away from 0, start outside
+ * 1 .. n_states - 1, or a state other than 0 that is reachable from the start
+ * and cannot reach an accepting state (so a viable prefix can always be
+ * completed over a vocabulary that holds every single byte).
+ *
+ * mwx_constraint_from_choices builds the byte trie of n texts: the accepted
+ * strings are the texts, each with (MWX_CONSTRAINT_LEADING_SPACE) one optional
+ * ' ' before it and (MWX_CONSTRAINT_TRAILING_PUNCT) one optional '.', '!' or
+ * '?' after it; with MWX_CONSTRAINT_FOLD_CASE an ASCII letter matches either
+ * case. NULL for n < 1, a null or empty text, unknown flag bits, or more than
+ * MWX_CONSTRAINT_MAX_STATES - 1 live states. */
+#define MWX_CONSTRAINT_MAX_STATES 4096
+#define MWX_CONSTRAINT_FOLD_CASE 1
+#define MWX_CONSTRAINT_LEADING_SPACE 2
+#define MWX_CONSTRAINT_TRAILING_PUNCT 4
+struct mwx_constraint;
+struct mwx_constraint* mwx_constraint_from_dfa(int n_states, int start, const uint16_t* trans,
+                                               const uint8_t* accepting);
+struct mwx_constraint* mwx_constraint_from_choices(const char* const* texts, int n, int flags);
+void mwx_constraint_free(struct mwx_constraint* c);
+/* Host-only queries. _accepting: 1 / 0 (0 for s out of range). _walk: the state
+ * after n bytes from s (0 for s out of range or a null argument). */
+int mwx_constraint_n_states(const struct mwx_constraint* c);
+int mwx_constraint_start(const struct mwx_constraint* c);
+int mwx_constraint_accepting(const struct mwx_constraint* c, int s);
+int mwx_constraint_walk(const struct mwx_constraint* c, int s, const uint8_t* bytes, int n);
+/* The last mwx_full* call on the state: -1 it had no constraint; 1 every
+ * decoded window's final sequence ended in an accepting state; 0 otherwise (a
+ * dead state, or a window that ended in a non-accepting state). */
+int mwx_full_constraint_status_from_state(struct mwx_state* state);
 
 #ifdef __cplusplus
 }

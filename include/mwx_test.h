@@ -550,6 +550,49 @@ int mwx_test_logits_bias(struct mwx_context* ctx, const struct mwx_bias_phrase* 
                          const int* hist_len, const int* active, const int* sample,
                          float* logits_out, int* state_out);
 
+/* --- constrained decoding (tests/test_constraint_ref.py,
+ * test_gpu_constraint_kernel.py) ----------------------------------------- */
+
+/* A constraint (csrc/constraint.h) built from choices (texts !=
+ * NULL: mwx_constraint_from_choices(texts, n, flags)) or else from a DFA
+ * (mwx_constraint_from_dfa(n_states, start, trans, accepting)), walked with the
+ * class-compressed table over bytes [n_bytes] from state `from` (< 0: the
+ * start). Needs no context and does no device work. Returns the state reached
+ * (0 = dead), or -1 when the constraint is refused or for n_bytes < 0 or
+ * bytes == NULL with n_bytes > 0. Nullable outputs: the state's accepting flag,
+ * the number of states (the dead one included), the number of byte classes,
+ * and the size in bytes of the block the device reads. */
+int mwx_test_constraint_walk(const char* const* texts, int n, int flags, int n_states, int start,
+                             const uint16_t* trans, const uint8_t* accepting, int from,
+                             const uint8_t* bytes, int n_bytes, int* accepting_out,
+                             int* n_states_out, int* n_classes_out, long long* table_bytes_out);
+
+/* One logits_constrain launch (csrc/k_constrain.hip) on R rows with the given
+ * constraint states, active [R] and sample [R]. The token byte table is the
+ * context's own vocabulary (tok_off == NULL: V must be mwx_n_vocab, eot is
+ * ignored) or a supplied one: the bytes of token t < eot are tok_bytes[
+ * tok_off[t] .. tok_off[t + 1]), tok_off [eot + 1] ascending from 0, eot <= V.
+ * Out: mask_out [R][ceil(V / 64)] 64-bit words, bit t % 64 of word t / 64 set
+ * = token t rejected. The hook owns the device buffers; the words start as
+ * all-ones bits, so a row the kernel does not write comes back as such, and lie
+ * between two guard bands of sentinel words. Returns 0; -1 without a launch
+ * for a null argument, R outside 1..256, V outside 1..53248, a state outside
+ * [0, n_states) or a malformed table; -2 on a device error; -3 if the launch
+ * changed a guard band. */
+int mwx_test_constraint_mask(struct mwx_context* ctx, const struct mwx_constraint* c, int R, int V,
+                             int eot, const uint32_t* tok_off, const uint8_t* tok_bytes,
+                             const int* state, const int* active, const int* sample,
+                             uint64_t* mask_out);
+
+/* mwx_test_logits_process with the filter's constrained-decoding arguments:
+ * cmask [R][ceil(V / 64)] rejection words and the penalty (finite, > 0; else
+ * -1 without a launch). Everything else as mwx_test_logits_process. */
+int mwx_test_logits_process_masked(struct mwx_context* ctx, int R, int V, const float* logits,
+                                   const float* smask, const struct mwx_test_logits_ctl* ctl,
+                                   const struct mwx_test_logits_const* lc, const uint64_t* cmask,
+                                   float penalty, float* flt, float* probs, float* logprobs,
+                                   struct mwx_test_logits_out* out);
+
 #ifdef __cplusplus
 }
 #endif

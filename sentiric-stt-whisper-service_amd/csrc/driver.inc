@@ -705,6 +705,49 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
     return s;
   };
 
+  // ---------------- constrained decoding (D15) ----------------
+  // the context's token byte table (first constrained call only) and the
+  // call's table block, uploaded once before the first window; the alignment
+  // pass and the detection above run without them. con_state: the state after
+  // a row's generated ids from the start state, the host's side of RowRun.con
+  // / RowCtl.pad[1]
+  const mwx_constraint* con = align ? nullptr : P.constraint;
+  ConBlock con_blk;
+  ConView con_h{};
+  if (con) {
+    {
+      std::lock_guard<std::mutex> lock(C.con_mu);
+      if (!C.con_tok_dev) {
+        C.con_tok = constraint_tokens(vb.id_to_token, vb.token_eot);
+        std::lock_guard<std::recursive_mutex> cap(capture_mutex());
+        uint8_t* d = nullptr;
+        HIPC(hipMalloc((void**)&d, C.con_tok.data.size()));
+        if (hipMemcpy(d, C.con_tok.data.data(), C.con_tok.data.size(), hipMemcpyHostToDevice) !=
+            hipSuccess) {
+          (void)hipFree(d);
+          MWX_LOG_ERROR("mwx: token byte table upload failed\n");
+          return -1;
+        }
+        C.con_tok_dev = d;
+      }
+    }
+    con_blk = constraint_block(*con);
+    uint8_t* d_blk = (uint8_t*)S.con_blk.get(con_blk.data.size());
+    HIPC(hipMemcpyAsync(d_blk, con_blk.data.data(), con_blk.data.size(), hipMemcpyHostToDevice,
+                        st));
+    con_h = constraint_view(*con, C.con_tok);
+    D.con_dev = constraint_view_dev(*con, con_blk, d_blk, C.con_tok, C.con_tok_dev);
+    D.con_penalty = P.constraint_penalty;
+  }
+  auto con_state = [&](const std::vector<mwx_token_data>& toks) {
+    if (!con) return 0;
+    int s = con->start;
+    for (const mwx_token_data& t : toks) s = con_next_state(con_h, s, t.id);
+    return s;
+  };
+  if (!align)
+    for (int c = 0; c < n_clips; ++c) states[c]->s.con_status = con ? 1 : -1;
+
   // ---------------- transcript alignment (D12) ----------------
   if (align) {
     // the clips mwx_full_batch would decode a window of, at seek 0
@@ -903,6 +946,7 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
         memcpy(pin + off, src, bytes);
         HIPC(hipMemcpyAsync(dst, pin + off, bytes, hipMemcpyHostToDevice, st));
       };
+      if (con) S.con_mask.get((size_t)R * ((V + 63) / 64) * 8);  // (before any graph capture)
       if (host_probs) {
         S.probs.get((size_t)R * V * 4);  // allocate before any graph capture
         S.logprobs.get((size_t)R * V * 4);
@@ -965,6 +1009,7 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
           k.temperature = t_cur;
           k.want_nosp = (k.sample && k.is_initial) ? 1 : 0;
           k.pad[0] = bias_state(w.tokens);
+          k.pad[1] = con_state(w.tokens);
         }
       };
       // run-ahead (every decode mode: greedy, temperature sampling, beam
@@ -1195,6 +1240,7 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
           x.seek_end = cr.seek_end;
           x.sum = w.sum_logprobs_all;
           x.pad = bias_state(w.tokens);
+          x.con = con_state(w.tokens);
           std::copy(cr.prompt.begin(), cr.prompt.end(), rp + (size_t)r * D.Tctx);
         }
         constexpr int NS = State::RUN_SLOTS;
@@ -1277,6 +1323,7 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
         rc.temperature = t_cur;
         rc.want_probs = host_probs ? 1 : 0;
         rc.bias = D.bias_dev;
+        rc.con = D.con_dev;
         for (int i = 0; i < NS; ++i)
           if (!S.ev_step[i]) HIPC(hipEventCreateWithFlags(&S.ev_step[i], hipEventDisableTiming));
         bool instr_of[NS] = {};
@@ -1431,6 +1478,10 @@ static int run_full(Context& C, mwx_state* const* states, mwx_full_params P,
         dtw_seg0[c] = cs.result_all.size();
       }
       const Row& best = best_row[c];
+      if (con) {  // (mwx_full_constraint_status_from_state)
+        const int s_end = con_state(best.tokens);
+        if (!(s_end > 0 && con->acc[s_end])) cs.con_status = 0;
+      }
       const int seek_delta = best.seek_delta;
       const int result_len = best.result_len;
       const auto& toks = best.tokens;
@@ -1780,7 +1831,7 @@ void mwx_free_state(struct mwx_state* state) {
                        &S.pf_pres, &S.pf_pq, &S.perf_span,
                        &S.dtw_kself, &S.dtw_vself, &S.dtw_w, &S.dtw_cost, &S.dtw_frames,
                        &S.dtw_meta, &S.xkeys, &S.sc_in, &S.sc_h, &S.sc_logits, &S.sc_out,
-                       &S.bias_tab};
+                       &S.bias_tab, &S.con_blk, &S.con_mask};
   for (auto* b : bufs) b->release();
   if (S.pin) (void)hipHostFree(S.pin);
   S.pin = nullptr;
@@ -1808,6 +1859,7 @@ void mwx_free(struct mwx_context* ctx) {
   if (ctx->c.arena) (void)hipFree(ctx->c.arena);
   if (ctx->c.gelu_tab) (void)hipFree(ctx->c.gelu_tab);
   if (ctx->c.dtw_dev) (void)hipFree(ctx->c.dtw_dev);
+  if (ctx->c.con_tok_dev) (void)hipFree(ctx->c.con_tok_dev);
   delete ctx;
 }
 
@@ -1866,6 +1918,8 @@ struct mwx_full_params mwx_full_default_params(int strategy) {
   p.bench_fixed_steps = 0;
   p.bias_phrases = nullptr;
   p.n_bias_phrases = 0;
+  p.constraint = nullptr;
+  p.constraint_penalty = 100.0f;
   return p;
 }
 
@@ -1892,7 +1946,11 @@ static int bias_check(const Vocab& vb, const mwx_full_params& P, const char* fn)
   const char* why = "";
   const int rc = bias_validate(P.bias_phrases, P.n_bias_phrases, vb.token_eot, &why);
   if (rc == -1) MWX_LOG_ERROR("%s: bias_phrases: %s\n", fn, why);
-  return rc;
+  if (rc) return rc;
+  // mwx_full_params.constraint / constraint_penalty (mwx.h; DESIGN.md D15)
+  const int rc2 = constraint_check(P, &why);
+  if (rc2) MWX_LOG_ERROR("%s: constraint: %s\n", fn, why);
+  return rc2;
 }
 }  // namespace mwx
 
@@ -2030,6 +2088,7 @@ int mwx_full_batch_trimmed(struct mwx_context* ctx, struct mwx_state* const* sta
     states[b]->s.result_all.clear();
     states[b]->s.lang_probs.clear();
     states[b]->s.lang_last.clear();
+    states[b]->s.con_status = params.constraint ? 1 : -1;  // (no window: nothing missed)
     if (c.seg.empty() || c.n_compact <= 0) continue;
     if (params.lang_ids) run_ids.push_back(params.lang_ids[b]);
     run_states.push_back(states[b]);
@@ -2189,6 +2248,8 @@ int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* sta
   }
   bool any_lang = false;
   for (int b = 0; b < n_clips; ++b) any_lang = any_lang || entry_lang[b] >= 0;
+  // constrained decoding: an entry's status is the worst of its chunks'
+  std::vector<int> con_st((size_t)n_clips, params.constraint ? 1 : -1);
   for (size_t r0 = 0; r0 < jobs.size() && rc == 0; r0 += width) {
     const size_t n = std::min(width, jobs.size() - r0);
     if (r0 > 0 && mwx::aborted(params)) {
@@ -2220,6 +2281,7 @@ int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* sta
         acc[jb.entry].push_back(std::move(sg));
       }
       rs.result_all.clear();
+      if (params.constraint && rs.con_status == 0) con_st[jb.entry] = 0;
       if (jb.chunk == 0) {
         lang[jb.entry] = rs.lang_id;
         if (!pooled[jb.entry]) lprobs[jb.entry] = rs.lang_probs;
@@ -2232,6 +2294,7 @@ int mwx_full_batch_chunked(struct mwx_context* ctx, struct mwx_state* const* sta
   }
   for (int b = 0; b < n_clips; ++b) states[b]->s.result_all.clear();
   if (rc != 0) return rc;
+  for (int b = 0; b < n_clips; ++b) states[b]->s.con_status = con_st[b];
   for (int b = 0; b < n_clips; ++b) {
     if (lang[b] < 0) continue;
     states[b]->s.result_all = std::move(acc[b]);
@@ -2517,6 +2580,11 @@ int mwx_full_lang_probs_from_state(struct mwx_state* state, float* probs, int n)
 const char* mwx_token_to_str(struct mwx_context* ctx, mwx_token token) {
   return ctx->c.vocab.id_to_token.at(token).c_str();
 }
+int mwx_full_constraint_status_from_state(struct mwx_state* state) {
+  return state ? state->s.con_status : -1;
+}
+// (constraint.cpp's refusal reasons go to the engine's log sink)
+extern "C" void mwx_constraint_log(const char* msg) { MWX_LOG_ERROR("%s\n", msg); }
 mwx_token mwx_token_eot(struct mwx_context* ctx) { return ctx->c.vocab.token_eot; }
 mwx_token mwx_token_sot(struct mwx_context* ctx) { return ctx->c.vocab.token_sot; }
 mwx_token mwx_token_beg(struct mwx_context* ctx) { return ctx->c.vocab.token_beg; }
@@ -3786,12 +3854,12 @@ extern "C" int mwx_test_gelu_table(struct mwx_context* ctx, uint16_t* out) {
 // ---------------------------------------------------------------------------
 // Logits processing on given data (mwx_test_logits_process / _setup)
 // ---------------------------------------------------------------------------
-extern "C" int mwx_test_logits_process(struct mwx_context* ctx, int R, int V, const float* logits,
-                                       const float* smask,
-                                       const struct mwx_test_logits_ctl* ctl,
-                                       const struct mwx_test_logits_const* lc, float* flt,
-                                       float* probs, float* logprobs,
-                                       struct mwx_test_logits_out* out) {
+static int test_logits_process_impl(struct mwx_context* ctx, int R, int V, const float* logits,
+                                    const float* smask, const struct mwx_test_logits_ctl* ctl,
+                                    const struct mwx_test_logits_const* lc, float* flt,
+                                    float* probs, float* logprobs,
+                                    struct mwx_test_logits_out* out, const uint64_t* cmask,
+                                    float cpenalty) {
   if (!ctx || !logits || !smask || !ctl || !lc || !flt || !probs || !logprobs || !out) return -1;
   if (R < 1 || R > 256 || V < 1 || lc->n_vocab != V) return -1;
   auto in_v = [&](int i) { return i >= 0 && i < V; };
@@ -3841,7 +3909,14 @@ extern "C" int mwx_test_logits_process(struct mwx_context* ctx, int R, int V, co
     float* dp = (float*)gp.make(m, rv, nullptr);
     float* dlp = (float*)gl.make(m, rv, nullptr);
     mwx::TokOut* dout = (mwx::TokOut*)go.make(m, (size_t)R * sizeof(mwx::TokOut), nullptr);
-    mwx::logits_process(dl, dm, dc, dout, dp, dlp, C, R, ws, nullptr, true);
+    unsigned long long* dcm = nullptr;
+    if (cmask) {  // (constrained decoding: the filter's mask and penalty arguments)
+      const size_t mb = (size_t)R * ((V + 63) / 64) * 8;
+      dcm = (unsigned long long*)m.get(mb);
+      HIPC(hipMemcpy(dcm, cmask, mb, hipMemcpyHostToDevice));
+    }
+    mwx::logits_process(dl, dm, dc, dout, dp, dlp, C, R, ws, nullptr, true, dcm,
+                        dcm ? cpenalty : 0.0f);
     HIPC(hipGetLastError());
     HIPC(hipDeviceSynchronize());
     std::vector<mwx::TokOut> ho(R);
@@ -3866,6 +3941,27 @@ extern "C" int mwx_test_logits_process(struct mwx_context* ctx, int R, int V, co
   } catch (...) {
     return -2;
   }
+}
+
+extern "C" int mwx_test_logits_process(struct mwx_context* ctx, int R, int V, const float* logits,
+                                       const float* smask,
+                                       const struct mwx_test_logits_ctl* ctl,
+                                       const struct mwx_test_logits_const* lc, float* flt,
+                                       float* probs, float* logprobs,
+                                       struct mwx_test_logits_out* out) {
+  return test_logits_process_impl(ctx, R, V, logits, smask, ctl, lc, flt, probs, logprobs, out,
+                                  nullptr, 0.0f);
+}
+extern "C" int mwx_test_logits_process_masked(struct mwx_context* ctx, int R, int V,
+                                              const float* logits, const float* smask,
+                                              const struct mwx_test_logits_ctl* ctl,
+                                              const struct mwx_test_logits_const* lc,
+                                              const uint64_t* cmask, float penalty, float* flt,
+                                              float* probs, float* logprobs,
+                                              struct mwx_test_logits_out* out) {
+  if (!cmask || !std::isfinite(penalty) || !(penalty > 0.0f)) return -1;
+  return test_logits_process_impl(ctx, R, V, logits, smask, ctl, lc, flt, probs, logprobs, out,
+                                  cmask, penalty);
 }
 
 extern "C" int mwx_test_logits_setup(struct mwx_context* ctx, const struct mwx_full_params* params,
@@ -4248,6 +4344,61 @@ extern "C" int mwx_test_logits_bias(struct mwx_context* ctx, const struct mwx_bi
     if (!gl.take(hl.data()) || !gs.take(hs.data())) return -3;
     memcpy(logits_out, hl.data(), hl.size() * 4);
     memcpy(state_out, hs.data(), hs.size() * 4);
+    return 0;
+  } catch (...) {
+    return -2;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Constrained decoding on given data (k_constrain.hip; mwx_test_constraint_walk
+// is in constraint.cpp: it needs no device)
+// ---------------------------------------------------------------------------
+extern "C" int mwx_test_constraint_mask(struct mwx_context* ctx, const struct mwx_constraint* c,
+                                        int R, int V, int eot, const uint32_t* tok_off,
+                                        const uint8_t* tok_bytes, const int* state,
+                                        const int* active, const int* sample, uint64_t* mask_out) {
+  if (!ctx || !c || !state || !active || !sample || !mask_out) return -1;
+  if (R < 1 || R > 256 || V < 1 || V > mwx::LP_G * mwx::LP_CHUNK) return -1;
+  if (tok_off) {
+    if (eot < 0 || eot > V || (!tok_bytes && tok_off[eot] > 0) || tok_off[0] != 0) return -1;
+    for (int t = 0; t < eot; ++t)
+      if (tok_off[t + 1] < tok_off[t]) return -1;
+  } else {
+    if (V != ctx->c.hp.n_vocab) return -1;
+    eot = ctx->c.vocab.token_eot;
+  }
+  for (int r = 0; r < R; ++r)
+    if (state[r] < 0 || state[r] >= c->S) return -1;
+  try {
+    HIPC(hipSetDevice(ctx->c.device));
+    const mwx::ConTokens tk = tok_off ? mwx::constraint_tokens_raw(tok_off, tok_bytes, eot)
+                                      : mwx::constraint_tokens(ctx->c.vocab.id_to_token, eot);
+    const mwx::ConBlock blk = mwx::constraint_block(*c);
+    std::vector<mwx::RowCtl> hc(R);
+    for (int r = 0; r < R; ++r) {
+      memset(&hc[r], 0, sizeof(mwx::RowCtl));
+      hc[r].active = active[r];
+      hc[r].sample = sample[r];
+      hc[r].pad[1] = state[r];
+    }
+    DevScratch m;
+    uint8_t* db = (uint8_t*)m.get(blk.data.size());
+    uint8_t* dt = (uint8_t*)m.get(tk.data.size());
+    mwx::RowCtl* dc = (mwx::RowCtl*)m.get((size_t)R * sizeof(mwx::RowCtl));
+    HIPC(hipMemcpy(db, blk.data.data(), blk.data.size(), hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dt, tk.data.data(), tk.data.size(), hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dc, hc.data(), (size_t)R * sizeof(mwx::RowCtl), hipMemcpyHostToDevice));
+    const size_t mb = (size_t)R * ((V + 63) / 64) * 8;
+    GuardedBuf gm;
+    unsigned long long* dm = (unsigned long long*)gm.make(m, mb, nullptr);
+    const mwx::ConView v = mwx::constraint_view_dev(*c, blk, db, tk, dt);
+    if (!mwx::logits_constrain(dm, dc, v, R, V, nullptr)) return -1;
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    std::vector<uint8_t> hm(mb);
+    if (!gm.take(hm.data())) return -3;
+    memcpy(mask_out, hm.data(), mb);
     return 0;
   } catch (...) {
     return -2;

@@ -29,6 +29,7 @@
 
 #include "bias.h"
 #include "common.h"
+#include "constraint.h"
 #include "kernels.h"
 #include "vad_trim.h"
 
@@ -169,6 +170,12 @@ struct Context {
   std::vector<std::pair<int, int>> dtw_heads;
   int2* dtw_dev = nullptr;
   std::vector<int> dtw_off, dtw_cnt;  // per decoder layer: first pair, pairs
+  // constrained decoding: the byte table of the ids below eot
+  // (constraint.h), built and uploaded under con_mu by the first call that
+  // carries a constraint; a context that never sees one allocates nothing
+  std::mutex con_mu;
+  ConTokens con_tok;
+  uint8_t* con_tok_dev = nullptr;
 };
 
 struct Segment {
@@ -270,6 +277,10 @@ struct State {
   long n_ra_fallback = 0;
   DBuf lpflt, lpparts, lpres;  // logits-processing scratch
   DBuf bias_tab;               // contextual biasing: the call's matcher tables (bias.h)
+  // constrained decoding (D15): the call's table block, the step's rejection
+  // words [rows][ceil(V / 64)], and mwx_full_constraint_status_from_state
+  DBuf con_blk, con_mask;
+  int con_status = -1;
   // beam search KV hand-over without copies: per row, positions below
   // kvown[row] are read from row kvmap[row][pos] (host copies in kvmap_h/kvown_h)
   DBuf kvmap, kvown;
@@ -939,6 +950,10 @@ struct Driver {
   // contextual biasing: the call's matcher tables on the
   // device, set for the window loop only; nullptr = no phrases, no launch
   const int* bias_dev = nullptr;
+  // constrained decoding: the call's tables on the device, set
+  // for the window loop only; tab == nullptr = no constraint, no launch
+  ConView con_dev{};
+  float con_penalty = 0.0f;
   PickIn pick_in() const {
     PickIn p;
     p.logits = (const float*)S.logits.p;
@@ -1987,12 +2002,21 @@ struct Driver {
                        V, s))
         throw std::runtime_error("mwx: logits_bias refused its launch");
     }
+    const unsigned long long* cmask = nullptr;
+    if (con_dev.tab) {  // (a call without a constraint captures the same graph as ever)
+      PerfScope pc(S, "logits_constrain", s);
+      unsigned long long* m = (unsigned long long*)S.con_mask.p + (size_t)r0 * ((V + 63) / 64);
+      if (!S.con_mask.p ||
+          !logits_constrain(m, (const RowCtl*)S.ctl.p + r0, con_dev, n, V, s))
+        throw std::runtime_error("mwx: logits_constrain refused its launch");
+      cmask = m;
+    }
     PerfScope ps(S, "logits_proc", s);
     logits_process((float*)S.logits.p + (size_t)r0 * V, (const float*)S.smask.p,
                    (const RowCtl*)S.ctl.p + r0, (TokOut*)S.tokout.p + r0, pr, lp, LC, n,
                    LPScratch{(float*)S.lpflt.p + (size_t)r0 * V, (LPPart*)S.lpparts.p + r0 * LP_G,
                              (LPRes*)S.lpres.p + r0 * LP_G},
-                   s, !pick_in_advance);
+                   s, !pick_in_advance, cmask, cmask ? con_penalty : 0.0f);
     if (want_probs) {  // std::discrete_distribution draws of the sampling rows
       const int KD = S.draw_k;
       sample_draws(pr, lp, V, (const double*)S.du.p + (size_t)r0 * KD, (const int*)S.dnd.p + r0,

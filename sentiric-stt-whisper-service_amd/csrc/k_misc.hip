@@ -12,6 +12,8 @@
 
 #define MWX_BIAS_NO_HOST  // (the transition only)
 #include "bias.h"
+#define MWX_CON_NO_HOST
+#include "constraint.h"
 #include "kcommon.h"
 #include "kernels.h"
 #include "ln_core.h"
@@ -339,7 +341,9 @@ __global__ __launch_bounds__(LP_T) void lp_filter_kernel(const float* __restrict
                                                          const RowCtl* __restrict__ ctl,
                                                          float* __restrict__ flt,
                                                          LPPart* __restrict__ parts,
-                                                         LogitsConst C) {
+                                                         LogitsConst C,
+                                                         const unsigned long long* __restrict__ cmask,
+                                                         float cpenalty) {
   __shared__ float red[4];
   __shared__ float red3[3][4];
   const int row = blockIdx.y, ch = blockIdx.x;
@@ -351,6 +355,8 @@ __global__ __launch_bounds__(LP_T) void lp_filter_kernel(const float* __restrict
   float* F = flt + (long)row * V;
   const int tid0_init = C.max_initial_tid;
   const int ts_lo = C.beg + c.seek_delta / 2;
+  // constrained decoding (D15): the row's rejection words, nullptr = off
+  const unsigned long long* cm = cmask ? cmask + (long)row * ((V + 63) >> 6) : nullptr;
   float x[LP_NPT], v[LP_NPT];
   float rmax = -INFINITY, m = -INFINITY, mtext = -INFINITY, mts = -INFINITY;
   sfor<0, LP_NPT>([&](auto kc) {
@@ -361,6 +367,7 @@ __global__ __launch_bounds__(LP_T) void lp_filter_kernel(const float* __restrict
     x[k] = in ? L[i] : -INFINITY;
     float y = x[k];
     if (c.temperature > 0.0f) y = y / c.temperature;
+    if (cm && in && ((cm[i >> 6] >> (i & 63)) & 1ull)) y = y - cpenalty;
     bool kill = !in || smask[i] < 0.0f;
     if (c.is_initial && C.suppress_blank && (i == C.eot || i == C.space_id)) kill = true;
     if (c.last_ts) {
@@ -573,9 +580,10 @@ __global__ __launch_bounds__(64) void lp_pick_kernel(const float* __restrict__ l
 
 void logits_process(float* logits, const float* static_mask, const RowCtl* ctl, TokOut* out,
                     float* probs, float* logprobs, const LogitsConst& C, int R, LPScratch ws,
-                    hipStream_t st, bool pick) {
+                    hipStream_t st, bool pick, const unsigned long long* cmask, float cpenalty) {
   const dim3 g(LP_G, R);
-  lp_filter_kernel<<<g, LP_T, 0, st>>>(logits, static_mask, ctl, ws.flt, ws.parts, C);
+  lp_filter_kernel<<<g, LP_T, 0, st>>>(logits, static_mask, ctl, ws.flt, ws.parts, C, cmask,
+                                       cpenalty);
   lp_probs_kernel<<<g, LP_T, 0, st>>>(ws.flt, ws.parts, ctl, ws.res, probs, logprobs, C);
   if (pick) lp_pick_kernel<<<R, 64, 0, st>>>(logits, ws.flt, ws.parts, ws.res, ctl, out, C);
 }
@@ -589,6 +597,7 @@ __device__ __forceinline__ void token_rules(RowRun& w, int id, const RunConst& C
   w.last_id = id;
   w.ntok = i + 1;
   w.pad = bias_next_state(C.bias, w.pad, id);  // contextual biasing (0 without phrases)
+  w.con = con_next_state(C.con, w.con, id);    // constrained decoding (0 without a constraint)
   bool stop = false;
   if (id > C.beg) {
     const int sd_new = 2 * (id - C.beg);
@@ -626,7 +635,7 @@ __device__ __forceinline__ RowCtl next_inputs(const RowRun& w, const RunConst& C
   n.temperature = C.temperature;
   n.want_nosp = (n.sample && n.is_initial) ? 1 : 0;
   n.pad[0] = w.pad;  // the biasing state the step's logits are boosted in
-  n.pad[1] = 0;
+  n.pad[1] = w.con;  // the constraint state the step's tokens are judged in
   return n;
 }
 
@@ -805,6 +814,7 @@ __global__ __launch_bounds__(BA_T) void beam_advance_kernel(RowRun* __restrict__
         w.ntok = p.ntok;
         w.last_id = p.last_id;
         w.pad = p.pad;
+        w.con = p.con;
         w.penult_id = p.penult_id;
         w.has_ts = p.has_ts;
         w.seek_delta = p.seek_delta;

@@ -1,5 +1,6 @@
 // Host-visible launcher declarations for the gfx950 kernels of the mwx engine.
 #pragma once
+#include "constraint.h"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -330,6 +331,7 @@ struct RowCtl {
   float temperature; // > 0: logits /= temperature
   int want_nosp;     // compute no_speech probability from the raw logits
   int pad[2];        // pad[0]: the row's contextual-biasing state (bias.h; 0 = root / off)
+                     // pad[1]: its constraint state (constraint.h; 0 = dead / off)
 };
 struct TokOut {
   int id;
@@ -360,15 +362,20 @@ struct RowRun {
   int cls;          // beam: token-sequence class (equal sequences <=> equal cls)
   int used;         // beam: uniforms of the row's RNG consumed so far
   int pad;          // contextual biasing: the matcher state after the generated ids (bias.h)
+  int con;          // constrained decoding: the state after the generated ids (constraint.h)
+  int pad2;
   double sum;       // beam: sum_logprobs_all
 };
+static_assert(sizeof(RowRun) == 72, "15 words, one of padding, and the sum");
 struct RunConst {
   int beg, eot, max_tokens, n_max, delta_min, R, nslot, prompt_stride;
   float temperature;
   int want_probs;
   const int* bias;  // contextual biasing: the call's matcher tables (bias.h), nullptr = off
+  ConView con;      // constrained decoding: the call's tables (constraint.h), tab == nullptr = off
 };
-static_assert(sizeof(RunConst) == 48, "the tables pointer takes the former pad words");
+static_assert(sizeof(RunConst) == 48 + sizeof(ConView) && sizeof(ConView) == 64,
+              "the bias pointer takes the former pad words; the constraint view follows");
 // what the host reads back per row and step (written straight into pinned
 // host memory by the advance kernel: no copy launch per step)
 struct RunReport {
@@ -457,10 +464,24 @@ struct LPScratch {
   LPRes* res;     // [R][LP_G]
 };
 // pick = false: phase 3 (lp_pick) is left to the run-ahead advance kernel
-// (PickIn)
+// (PickIn). cmask (nullable; constrained decoding): [R][ceil(
+// n_vocab / 64)] words of logits_constrain; where bit t of a row is set the
+// filter takes y - cpenalty for y = x / T (or x), before the kill rules; the
+// raw logits the no-speech probability is computed from are not touched.
+// nullptr: the arithmetic and its order are as without the argument.
 void logits_process(float* logits, const float* static_mask, const RowCtl* ctl, TokOut* out,
                     float* probs, float* logprobs, const LogitsConst& C, int R, LPScratch ws,
-                    hipStream_t st, bool pick = true);
+                    hipStream_t st, bool pick = true, const unsigned long long* cmask = nullptr,
+                    float cpenalty = 0.0f);
+
+// Constrained decoding (k_constrain.hip): for every row r with
+// ctl[r].active && ctl[r].sample, mask[r W + w] (W = ceil(V / 64)) gets bit b
+// set iff token 64 w + b < V is rejected in the row's state ctl[r].pad[1];
+// bits above V are zero, a row in state 0 gets zeros, other rows are not
+// written. One store per 64 tokens from a wave ballot. false (no launch) for a
+// null pointer, R < 1, V < 1 or v.eot > V.
+bool logits_constrain(unsigned long long* mask, const RowCtl* ctl, const ConView& v, int R, int V,
+                      hipStream_t st);
 
 // Contextual biasing (k_bias.hip): for every row r with
 // ctl[r].active && ctl[r].sample, logits[r V + t] += bias[t] for the tokens the

@@ -115,6 +115,7 @@ void* mwx_stt_new(const char* model_dir, const char* model_filename, int paralle
   try {
     settings_dtw_from_env(s);
     settings_hotwords_from_env(s);
+    settings_choices_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -142,6 +143,7 @@ void* mwx_stt_new_batched(const char* model_dir, const char* model_filename,
   try {
     settings_dtw_from_env(s);
     settings_hotwords_from_env(s);
+    settings_choices_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -178,6 +180,7 @@ void* mwx_stt_new_ex(const char* model_dir, const char* model_filename, int para
   try {
     settings_dtw_from_env(s);
     settings_hotwords_from_env(s);
+    settings_choices_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -210,6 +213,7 @@ void* mwx_stt_new_vad(const char* model_dir, const char* model_filename, int par
   try {
     settings_dtw_from_env(s);
     settings_hotwords_from_env(s);
+    settings_choices_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -242,6 +246,7 @@ void* mwx_stt_new_vad_trim(const char* model_dir, const char* model_filename,
   try {
     settings_dtw_from_env(s);
     settings_hotwords_from_env(s);
+    settings_choices_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -278,6 +283,7 @@ void* mwx_stt_new_stream_vad(const char* model_dir, const char* model_filename,
   try {
     settings_dtw_from_env(s);
     settings_hotwords_from_env(s);
+    settings_choices_from_env(s);
     return new SttEngine(s);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "SttEngine: %s\n", e.what());
@@ -548,6 +554,37 @@ static int transcribe_any(void* eng, const int16_t* pcm16, const float* pcmf, in
     }
     if (abort_calls) *abort_calls = *calls;
     const int r = emit(to_json(rs), out, cap);
+    return r < -1 ? r - 2 : r;
+  } catch (const EngineBusyException&) {
+    return -2;
+  } catch (...) {
+    return -1;
+  }
+}
+
+// SttEngine::transcribe over f32 PCM with RequestOptions::choices (constrained
+// decoding; choice_flags < 0 and choice_penalty < 0 keep the defaults):
+// {"choice_match": k, "results": [...]} with the results as
+// mwx_stt_transcribe_pcm16 writes them and k the results' choice_match (-1
+// when there is no result to carry it). Return codes as
+// mwx_stt_transcribe_pcm16.
+int mwx_stt_transcribe_choices_f32(void* eng, const float* pcm, int n, int sample_rate,
+                                   const char* const* choices, int n_choices, int choice_flags,
+                                   float choice_penalty, const char* language, int beam_size,
+                                   float temperature, char* out, int cap) {
+  RequestOptions o;
+  o.language = language ? language : "";
+  o.beam_size = beam_size;
+  o.temperature = temperature;
+  for (int i = 0; i < n_choices && choices; ++i) o.choices.emplace_back(choices[i] ? choices[i] : "");
+  if (choice_flags >= 0) o.choice_flags = choice_flags;
+  o.choice_penalty = choice_penalty;
+  try {
+    const auto rs = static_cast<SttEngine*>(eng)->transcribe(std::vector<float>(pcm, pcm + n),
+                                                             sample_rate, o);
+    const int match = rs.empty() ? -1 : rs[0].choice_match;
+    const int r = emit("{\"choice_match\":" + std::to_string(match) + ",\"results\":" +
+                           to_json(rs) + "}", out, cap);
     return r < -1 ? r - 2 : r;
   } catch (const EngineBusyException&) {
     return -2;

@@ -47,6 +47,9 @@
 #pragma weak mwx_align_batch
 #pragma weak mwx_align_row
 #pragma weak mwx_tokenize
+#pragma weak mwx_constraint_from_choices
+#pragma weak mwx_constraint_free
+#pragma weak mwx_full_constraint_status_from_state
 #pragma weak mwx_full_lang_id_from_state
 #pragma weak mwx_lang_str
 // ... and the language-probability calls: without them detect_language()
@@ -174,6 +177,14 @@ void settings_hotwords_from_env(Settings& s) {
     char* end = nullptr;
     const float b = std::strtof(v, &end);
     if (end != v && std::isfinite(b) && b >= 0.0f) s.hotword_boost = b;
+  }
+}
+
+void settings_choices_from_env(Settings& s) {
+  if (const char* v = std::getenv("STT_WHISPER_SERVICE_CHOICE_PENALTY")) {
+    char* end = nullptr;
+    const float b = std::strtof(v, &end);
+    if (end != v && std::isfinite(b) && b > 0.0f) s.choice_penalty = b;
   }
 }
 
@@ -313,6 +324,12 @@ std::string SttEngine::options_key(const RequestOptions& o) const {
     std::snprintf(hb, sizeof hb, "|hw%.9g", hotword_boost_of(o));
     key += hb;
     for (const std::string& w : o.hotwords) key += "|" + std::to_string(w.size()) + ":" + w;
+  }
+  if (!o.choices.empty()) {  // (no choices: the key as it always was)
+    char cb[64];
+    std::snprintf(cb, sizeof cb, "|ch%d,%.9g", o.choice_flags, choice_penalty_of(o));
+    key += cb;
+    for (const std::string& w : o.choices) key += "|" + std::to_string(w.size()) + ":" + w;
   }
   return key;
 }
@@ -514,6 +531,52 @@ void SttEngine::make_bias(const RequestOptions& options, BiasKeep& keep) const {
   for (const auto& t : keep.toks) keep.phrases.push_back({t.data(), (int)t.size(), boost});
 }
 
+// Constrained decoding (mwx_full_params.constraint).
+float SttEngine::choice_penalty_of(const RequestOptions& o) const {
+  const float p = o.choice_penalty >= 0.0f ? o.choice_penalty : settings_.choice_penalty;
+  return (std::isfinite(p) && p > 0.0f) ? p : 100.0f;
+}
+
+std::vector<std::string> SttEngine::kept_choices(const RequestOptions& o, bool warn) {
+  std::vector<std::string> kept;
+  for (const std::string& c : o.choices) {
+    if (c.empty() || c.find('\0') != std::string::npos) {
+      if (warn) std::fprintf(stderr, "SttEngine: a choice dropped (empty, or it holds a NUL)\n");
+      continue;
+    }
+    kept.push_back(c);
+  }
+  return kept;
+}
+
+std::shared_ptr<const mwx_constraint> SttEngine::constraint_of(const RequestOptions& o) const {
+  if (o.choices.empty()) return nullptr;
+  if (!mwx_constraint_from_choices || !mwx_constraint_free) {
+    std::fprintf(stderr, "SttEngine: choices ignored: the library has no mwx_constraint_*\n");
+    return nullptr;
+  }
+  std::string key = std::to_string(o.choice_flags);
+  for (const std::string& c : o.choices) key += "|" + std::to_string(c.size()) + ":" + c;
+  std::lock_guard<std::mutex> lock(con_mutex_);
+  auto it = con_cache_.find(key);
+  if (it != con_cache_.end()) return it->second;
+  const std::vector<std::string> kept = kept_choices(o, true);
+  std::shared_ptr<const mwx_constraint> con;
+  if (!kept.empty()) {
+    std::vector<const char*> texts;
+    for (const std::string& c : kept) texts.push_back(c.c_str());
+    if (mwx_constraint* raw =
+            mwx_constraint_from_choices(texts.data(), (int)texts.size(), o.choice_flags))
+      con = std::shared_ptr<const mwx_constraint>(
+          raw, [](const mwx_constraint* p) { mwx_constraint_free(const_cast<mwx_constraint*>(p)); });
+    else
+      std::fprintf(stderr, "SttEngine: choices refused by the engine; running unconstrained\n");
+  }
+  if (con_cache_.size() >= 64) con_cache_.clear();  // (callers in flight hold their own reference)
+  con_cache_[key] = con;
+  return con;
+}
+
 mwx_full_params SttEngine::make_params(const RequestOptions& options, std::string& target_lang,
                                        std::function<bool()>& abort_fn, BiasKeep& bias) const {
   const int beam = options.beam_size >= 0 ? options.beam_size : settings_.beam_size;
@@ -553,6 +616,15 @@ mwx_full_params SttEngine::make_params(const RequestOptions& options, std::strin
   if (!bias.phrases.empty()) {
     p.bias_phrases = bias.phrases.data();
     p.n_bias_phrases = (int)bias.phrases.size();
+  }
+  bias.constraint = constraint_of(options);
+  if (bias.constraint) {
+    p.constraint = bias.constraint.get();
+    p.constraint_penalty = choice_penalty_of(options);
+    // a closed answer is one untimed piece of text: timestamp tokens are never
+    // rejected (D15), and left on, their probability mass can outweigh every
+    // allowed text token (the timestamp-versus-text rule) and end a window empty
+    p.no_timestamps = true;
   }
   return p;
 }
@@ -649,6 +721,10 @@ std::vector<TranscriptionResult> SttEngine::collect(mwx_state* state, const std:
     r.arousal = r.affective.arousal;
     r.valence = r.affective.valence;
     r.speaker_id = seg_len[i] < 160 ? "?" : clusterer.assign_or_add(r.affective.speaker_vec);
+  }
+  if (mwx_full_constraint_status_from_state) {  // (RequestOptions::choices)
+    const int match = mwx_full_constraint_status_from_state(state);
+    for (TranscriptionResult& r : results) r.choice_match = match;
   }
   return results;
 }

@@ -29,6 +29,7 @@
 #include <cstdint>
 #include <deque>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <queue>
@@ -123,6 +124,10 @@ struct Settings {
   // when the request does not give one. 0 (default): biasing off. The effect
   // on recognition and a sensible range are unmeasured.
   float hotword_boost = 0.0f;
+  // Constrained decoding (mwx_full_params.constraint; DESIGN.md D15,
+  // INTEGRATION.md "Constrained decoding"): the penalty of a request's choices
+  // when the request does not give one. Finite and > 0; default 100.
+  float choice_penalty = 100.0f;
   // Streaming VAD for StreamSession (INTEGRATION.md "Streaming"),
   // both off by default and inert without a loaded VAD model or against a
   // library that lacks the mwx_vad_stream_* calls.
@@ -152,6 +157,9 @@ void settings_dtw_from_env(Settings& s);
 // STT_WHISPER_SERVICE_HOTWORD_BOOST (a finite number >= 0) into
 // Settings::hotword_boost; unset or malformed leaves the field as it is.
 void settings_hotwords_from_env(Settings& s);
+// STT_WHISPER_SERVICE_CHOICE_PENALTY (a finite number > 0) into
+// Settings::choice_penalty; unset or malformed leaves the field as it is.
+void settings_choices_from_env(Settings& s);
 
 // Owner of one mwx_vad_trimmed (vad_trim; defined in stt_engine.cpp).
 struct TrimmedAudio;
@@ -227,6 +235,17 @@ struct RequestOptions {
   // Settings::hotword_boost. A boost of 0 passes nothing to the engine.
   std::vector<std::string> hotwords;
   float hotword_boost = -1.0f;
+  // Constrained decoding: the closed set of answers the transcript is held to
+  // (one per window). An empty choice, or one with a NUL byte, is dropped with
+  // a warning; with none left, or a set the engine refuses (more than 4095
+  // states), the request runs unconstrained. choice_flags: MWX_CONSTRAINT_*.
+  // A request with choices decodes with no_timestamps (a closed answer is one
+  // untimed piece of text; timestamp tokens are outside the constraint).
+  // choice_penalty < 0: Settings::choice_penalty.
+  std::vector<std::string> choices;
+  int choice_flags = MWX_CONSTRAINT_FOLD_CASE | MWX_CONSTRAINT_LEADING_SPACE |
+                     MWX_CONSTRAINT_TRAILING_PUNCT;
+  float choice_penalty = -1.0f;
 };
 
 struct TranscriptionResult {
@@ -247,6 +266,9 @@ struct TranscriptionResult {
   // the probability the detection pass gave the language used (language
   // "auto"), -1 when the call did not detect
   float language_probability = -1.0f;
+  // mwx_full_constraint_status_from_state of the call: -1 no choices, 1 every
+  // window ended on one of them, 0 otherwise
+  int choice_match = -1;
 };
 
 // Transcript alignment (SttEngine::align; mwx.h mwx_align_batch, rule D12):
@@ -449,7 +471,16 @@ class SttEngine {
   struct BiasKeep {
     std::vector<std::vector<mwx_token>> toks;
     std::vector<mwx_bias_phrase> phrases;
+    std::shared_ptr<const mwx_constraint> constraint;  // (RequestOptions::choices)
   };
+  // Constrained decoding: the penalty the request resolves to, the choices it
+  // keeps, and their constraint (built once per distinct (flags, choices) and
+  // kept: requests of one batch key share it)
+  float choice_penalty_of(const RequestOptions& o) const;
+  static std::vector<std::string> kept_choices(const RequestOptions& o, bool warn);
+  std::shared_ptr<const mwx_constraint> constraint_of(const RequestOptions& o) const;
+  mutable std::mutex con_mutex_;
+  mutable std::map<std::string, std::shared_ptr<const mwx_constraint>> con_cache_;
   float hotword_boost_of(const RequestOptions& o) const;
   void make_bias(const RequestOptions& options, BiasKeep& keep) const;
   mwx_full_params make_params(const RequestOptions& options, std::string& target_lang,

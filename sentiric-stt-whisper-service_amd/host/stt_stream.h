@@ -94,6 +94,14 @@ class StreamSession {
     options_.hotword_boost = hotword_boost;
   }
 
+  // ... and the constrained-decoding fields (choices, choice_flags, choice_penalty)
+  void set_choices(const std::vector<std::string>& choices, int choice_flags = -1,
+                   float choice_penalty = -1.0f) {
+    options_.choices = choices;
+    if (choice_flags >= 0) options_.choice_flags = choice_flags;
+    options_.choice_penalty = choice_penalty;
+  }
+
   static constexpr size_t kMaxBufferSamples = 16000 * 30;  // src/grpc_server.cpp:132
 
  private:

@@ -149,6 +149,7 @@ class FullParams(C.Structure):
         ("lang_ids", C.POINTER(C.c_int)),
         ("chunk_language", C.c_int),
         ("bias_phrases", C.POINTER(BiasPhrase)), ("n_bias_phrases", C.c_int),
+        ("constraint", C.c_void_p), ("constraint_penalty", C.c_float),
     ]
 
 
@@ -240,6 +241,134 @@ class Prosody(C.Structure):
 
 
 _lib = None
+
+CONSTRAINT_MAX_STATES = 4096
+CONSTRAINT_FOLD_CASE = 1
+CONSTRAINT_LEADING_SPACE = 2
+CONSTRAINT_TRAILING_PUNCT = 4
+
+
+class Constraint:
+    """mwx_constraint (constrained decoding): a byte-level DFA.
+    from_dfa / from_choices raise ValueError where the library returns NULL."""
+
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+    @staticmethod
+    def _decl():
+        L = lib()
+        u16, u8 = C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)
+        L.mwx_constraint_from_dfa.restype = C.c_void_p
+        L.mwx_constraint_from_dfa.argtypes = [C.c_int, C.c_int, u16, u8]
+        L.mwx_constraint_from_choices.restype = C.c_void_p
+        L.mwx_constraint_from_choices.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int]
+        L.mwx_constraint_free.restype = None
+        L.mwx_constraint_free.argtypes = [C.c_void_p]
+        for name in ("n_states", "start"):
+            f = getattr(L, "mwx_constraint_" + name)
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p]
+        L.mwx_constraint_accepting.restype = C.c_int
+        L.mwx_constraint_accepting.argtypes = [C.c_void_p, C.c_int]
+        L.mwx_constraint_walk.restype = C.c_int
+        L.mwx_constraint_walk.argtypes = [C.c_void_p, C.c_int, u8, C.c_int]
+        return L
+
+    @classmethod
+    def from_dfa(cls, trans, accepting, start: int, n_states=None) -> "Constraint":
+        """trans [S][256] state ids, accepting [S] flags."""
+        trans = np.ascontiguousarray(trans, dtype=np.uint16)
+        accepting = np.ascontiguousarray(accepting, dtype=np.uint8)
+        S = int(trans.shape[0]) if n_states is None else int(n_states)
+        L = cls._decl()
+        ptr = L.mwx_constraint_from_dfa(S, int(start),
+                                        trans.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                        accepting.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if not ptr:
+            raise ValueError("mwx_constraint_from_dfa refused the automaton")
+        return cls(ptr)
+
+    @classmethod
+    def from_choices(cls, texts, flags: int = 0) -> "Constraint":
+        """texts: str (UTF-8 encoded) or bytes."""
+        bs = [t if isinstance(t, bytes) else t.encode("utf-8") for t in texts]
+        arr = (C.c_char_p * max(1, len(bs)))(*bs)
+        L = cls._decl()
+        ptr = L.mwx_constraint_from_choices(arr, len(bs), int(flags))
+        if not ptr:
+            raise ValueError("mwx_constraint_from_choices refused the texts")
+        return cls(ptr)
+
+    def free(self):
+        if self.ptr:
+            lib().mwx_constraint_free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    @property
+    def n_states(self) -> int:
+        return self._decl().mwx_constraint_n_states(self.ptr)
+
+    @property
+    def start(self) -> int:
+        return self._decl().mwx_constraint_start(self.ptr)
+
+    def accepting(self, s: int) -> bool:
+        return bool(self._decl().mwx_constraint_accepting(self.ptr, int(s)))
+
+    def walk(self, data: bytes, s=None) -> int:
+        """The state after `data` from s (None: the start)."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        L = self._decl()
+        return L.mwx_constraint_walk(self.ptr, self.start if s is None else int(s),
+                                     buf.ctypes.data_as(C.POINTER(C.c_uint8)), len(buf))
+
+
+def with_constraint(params: "FullParams", constraint, penalty=None) -> "FullParams":
+    """A copy of params with constraint (a Constraint or None) and, if given,
+    constraint_penalty set. The copy keeps the constraint alive (and the
+    caller's params its strings: keep that one too)."""
+    p = FullParams.from_buffer_copy(params)
+    p.constraint = None if constraint is None else constraint.ptr
+    if penalty is not None:
+        p.constraint_penalty = penalty
+    p._con_keep = (constraint, params, getattr(params, "_bias_keep", None))
+    return p
+
+
+def constraint_walk_hook(data: bytes, texts=None, flags: int = 0, trans=None, accepting=None,
+                         start: int = 0, from_state: int = -1):
+    """mwx_test_constraint_walk (host only): builds the constraint from choices
+    (texts) or from a DFA and walks data. Returns (state or -1, accepting flag,
+    n_states, n_classes, table bytes)."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    u16, u8 = C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)
+    fn = lib().mwx_test_constraint_walk
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, u16, u8, C.c_int, u8,
+                   C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                   C.POINTER(C.c_longlong)]
+    acc, ns, nc, nb = C.c_int(-1), C.c_int(-1), C.c_int(-1), C.c_longlong(-1)
+    if texts is not None:
+        bs = [t if isinstance(t, bytes) else t.encode("utf-8") for t in texts]
+        arr = (C.c_char_p * max(1, len(bs)))(*bs)
+        rc = fn(arr, len(bs), int(flags), 0, 0, u16(), u8(), from_state,
+                buf.ctypes.data_as(u8), len(buf), C.byref(acc), C.byref(ns), C.byref(nc),
+                C.byref(nb))
+    else:
+        trans = np.ascontiguousarray(trans, dtype=np.uint16)
+        accepting = np.ascontiguousarray(accepting, dtype=np.uint8)
+        rc = fn(C.POINTER(C.c_char_p)(), 0, 0, int(trans.shape[0]), int(start),
+                trans.ctypes.data_as(u16), accepting.ctypes.data_as(u8), from_state,
+                buf.ctypes.data_as(u8), len(buf), C.byref(acc), C.byref(ns), C.byref(nc),
+                C.byref(nb))
+    return rc, acc.value, ns.value, nc.value, nb.value
 
 
 def bias_state(phrases, hist) -> int:
@@ -1118,6 +1247,11 @@ class Context:
         """special token id: eot, sot, beg, not, nosp, transcribe, translate"""
         return getattr(lib(), f"mwx_token_{name}")(self.ctx)
 
+    def token_bytes(self, ids) -> List[bytes]:
+        """mwx_token_to_str of every id, as bytes."""
+        L = lib()
+        return [L.mwx_token_to_str(self.ctx, int(t)) or b"" for t in ids]
+
     def test_mel(self, pcm: np.ndarray, state_index: int = 0) -> np.ndarray:
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         n_mels = self.hparam("n_mels")
@@ -1752,6 +1886,73 @@ class Context:
         rc = fn(self.ctx, R, V, fptr(logits), fptr(smask), ctl.ctypes.data, C.byref(lc),
                 fptr(flt), fptr(probs), fptr(logprobs), out.ctypes.data)
         return rc, flt, probs, logprobs, out
+
+    def test_logits_process_masked_rc(self, logits: np.ndarray, smask: np.ndarray,
+                                      ctl: np.ndarray, lc: TestLogitsConst, cmask: np.ndarray,
+                                      penalty: float):
+        """mwx_test_logits_process_masked: as test_logits_process_rc with the
+        filter's rejection words cmask [R][ceil(V / 64)] uint64 and the penalty."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        smask = np.ascontiguousarray(smask, dtype=np.float32)
+        ctl = np.ascontiguousarray(ctl, dtype=LOGITS_CTL)
+        cmask = np.ascontiguousarray(cmask, dtype=np.uint64)
+        R, V = logits.shape
+        assert smask.shape == (V,) and ctl.shape == (R,) and cmask.shape == (R, (V + 63) // 64)
+        flt, probs, logprobs = (np.full((R, V), np.nan, np.float32) for _ in range(3))
+        out = np.zeros(R, LOGITS_OUT)
+        out.view(np.uint32)[:] = 0xFFFFFFFF
+        fn = lib().mwx_test_logits_process_masked
+        fpp = C.POINTER(C.c_float)
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, fpp, fpp, C.c_void_p,
+                       C.POINTER(TestLogitsConst), C.c_void_p, C.c_float, fpp, fpp, fpp,
+                       C.c_void_p]
+        rc = fn(self.ctx, R, V, fptr(logits), fptr(smask), ctl.ctypes.data, C.byref(lc),
+                cmask.ctypes.data, float(penalty), fptr(flt), fptr(probs), fptr(logprobs),
+                out.ctypes.data)
+        return rc, flt, probs, logprobs, out
+
+    def test_constraint_mask_rc(self, constraint: "Constraint", states, active, sample,
+                                V=None, eot: int = 0, tokens=None):
+        """mwx_test_constraint_mask: one logits_constrain launch on R rows in the
+        given constraint states. tokens: None (the context's vocabulary; V its
+        n_vocab) or a list of the byte strings of the ids below eot = len(tokens)
+        (then V must be given). Returns (rc, mask [R][ceil(V / 64)] uint64); a
+        word the launch did not write is all ones."""
+        states = np.ascontiguousarray(states, dtype=np.int32)
+        active = np.ascontiguousarray(active, dtype=np.int32)
+        sample = np.ascontiguousarray(sample, dtype=np.int32)
+        R = len(states)
+        assert active.shape == (R,) and sample.shape == (R,)
+        u32, u8, ip = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+        if tokens is None:
+            V = self.hparam("n_vocab") if V is None else V
+            offp, bytp, eot = u32(), u8(), 0
+            keep = None
+        else:
+            eot = len(tokens)
+            off = np.zeros(eot + 1, np.uint32)
+            off[1:] = np.cumsum([len(t) for t in tokens], dtype=np.uint64)
+            data = np.frombuffer(b"".join(tokens) + b"\0", dtype=np.uint8)
+            offp, bytp, keep = off.ctypes.data_as(u32), data.ctypes.data_as(u8), (off, data)
+        W = (max(V, 1) + 63) // 64
+        mask = np.full((max(R, 1), W), 0xFFFFFFFFFFFFFFFF, np.uint64)
+        fn = lib().mwx_test_constraint_mask
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, u32, u8, ip, ip, ip,
+                       C.c_void_p]
+        rc = fn(self.ctx, None if constraint is None else constraint.ptr, R, V, eot, offp, bytp,
+                states.ctypes.data_as(ip), active.ctypes.data_as(ip), sample.ctypes.data_as(ip),
+                mask.ctypes.data)
+        del keep
+        return rc, mask
+
+    def constraint_status(self, state_index: int = 0) -> int:
+        """mwx_full_constraint_status_from_state."""
+        fn = lib().mwx_full_constraint_status_from_state
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p]
+        return fn(self.state(state_index))
 
     def test_logits_process(self, logits, smask, ctl, lc):
         """As test_logits_process_rc, raising on a non-zero return."""
